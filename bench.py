@@ -2,13 +2,21 @@
 Aiyagari VFI, Na = 20,000, Nz = 7 Rouwenhorst, one exhaustive Bellman sweep per step
 (Aiyagari_VFI.m:70-83) on the MI355X, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline needs: set up, W warm-up sweeps, one timed block of
+exactly K sweeps, the result line (metric, value, unit, ms_per_step, ...).  --dump-outputs DIR
+writes what the last timed sweep returned (v_new, policy_k, policy_c, idx) as DIR/<name>.npy;
+the inputs are the fixed calibration and v = 0, so two builds run with the same arguments can
+be compared array for array.  Everything else is behind --full: the median of 5 timed blocks,
+the kernel-event block and work counters behind the roofline, the legs below, the CPU
+baselines, and the detail file.
 
 Multi-GPU: the Aiyagari sweep does not shard (replicas only), so every rank
 runs the same sweeps (weak scaling, no collective on the data path; --distinct-r gives each
 rank its own GE candidate r instead); the timing is max over ranks.  Rank 0 prints one JSON
-line.  The line also carries `ks_sharded` (BASELINE configs[4]): one VFI iteration of the
+line.  With --full the line also carries `ks_sharded` (BASELINE configs[4]): one VFI iteration of the
 Krusell-Smith solve at k = 32,768, K = 64 sharded over the same N ranks ((K, Z) slices, one
 ghost-rectangle exchange per block of 4 Howard sweeps on > 1 rank; strong scaling), and
 `ge_batch` (configs[3]: multisection GE, candidates round-robin over the ranks, one all-gather
@@ -201,12 +209,68 @@ def _counters(name, traffic_name=None):
     return None, None, None
 
 
+def headline(args, cal, world, r, w, dt, blocks):
+    """The result of the timed blocks (`blocks`: wall s of each, `dt`: their median, max over
+    ranks): the contract fields, the workload and the block statistics."""
+    N, Na = cal["N"], cal["Na"]
+    step_ms = sorted(blocks)
+    return {
+        "metric": "Bellman evals/sec (Na·Na'·Nz, fp64)",
+        "value": world * N * Na * Na * args.steps / dt,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (reference calibration: Rouwenhorst Nz=7, quadratic grid)",
+        "config": {"workload": f"aiyagari_vfi_sweep Na={Na} Nz={N} rouwenhorst"
+                               + (" (BASELINE configs[1])" if (Na, N) == (20000, 7) else ""),
+                   "Na": Na, "Nz": N, "sigma": cal["sigma"], "beta": cal["beta"],
+                   "search": "exhaustive over a' (exact bound-tree screen)" if args.mode == 1
+                             else "exhaustive over a' (plain)",
+                   "sweeps_timed": f"sweeps {args.warmup + 1}..{args.warmup + args.steps} of a "
+                                   f"solve from v=0, hint = previous argmax",
+                   "parallelism": (f"replicas: one GE candidate r per rank ({world})"
+                                   if world > 1 and args.distinct_r else
+                                   f"replicas: the same sweeps (r = 0.04) on each of {world} "
+                                   f"rank(s), no data-path collective")},
+        "repeats": {"n": len(blocks), "median_ms_per_step": step_ms[len(blocks) // 2]
+                    / args.steps * 1e3, "min_ms_per_step": step_ms[0] / args.steps * 1e3,
+                    "max_ms_per_step": step_ms[-1] / args.steps * 1e3},
+    }
+
+
+def dump_outputs(path, **arrays):
+    """--dump-outputs: each device array as <path>/<name>.npy (float64; the int32 argmax
+    index too, exactly).  A sweep's four outputs are 4.5 MB at Na = 20,000; past 64 MB in all
+    (--na far above the headline's) every array keeps the same seeded sample of its entries."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: x.detach().cpu().numpy().astype(np.float64) for k, x in arrays.items()}
+    cap = (64 << 20) // 8 // len(host)
+    for k, x in host.items():
+        if x.size > cap:
+            x = x.ravel()[np.sort(np.random.RandomState(0).choice(x.size, cap, replace=False))]
+        np.save(os.path.join(path, f"{k}.npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks for the median (D7)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline's one timed block: 5 repeats, the "
+                         "kernel-event and counter passes (roofline), every leg, the CPU "
+                         "baselines, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed sweep returned as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps sweeps, value = the median block (D7); "
+                         "default 1, with --full 5")
     ap.add_argument("--na", type=int, default=20000)
     ap.add_argument("--mode", type=int, default=1, help="1 screened exhaustive, 2 plain")
     ap.add_argument("--k-chunk", type=int, default=1024)
@@ -233,6 +297,8 @@ def main():
                     help="launcher/contract check without a GPU: gloo ranks, a trivial timed "
                          "CPU loop, the same barrier/max-over-ranks/contract line")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     raise_hw_queues()
 
     import bench_launch
@@ -331,20 +397,25 @@ def main():
     # value: the median block (median of >= 5 timed repeats after the warm-up); every
     # block is exactly `steps` sweeps between barrier + synchronize, and the first is reported too
     dt = sorted(blocks)[len(blocks) // 2]
-    # the dominant kernel's average launch duration: HIP events around each launch of the same
-    # sweeps, in a block of their own
-    restore()
-    dt_ev, kern_avg_ms = timed_block(True)
-    # untimed instrumented pass: per-state work counters of the same sweeps
-    restore()
-    ws.set_timing(False, count=True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    counters = ws.counters()
-    ws.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed sweep returned to its caller (every block ends in the same state)
+        dump_outputs(args.dump_outputs, v_new=v[cur], policy_k=pk, policy_c=pc, idx=idx)
+    dt_ev = kern_avg_ms = counters = None
+    if args.full:
+        # the dominant kernel's average launch duration: HIP events around each launch of the
+        # same sweeps, in a block of their own
+        restore()
+        dt_ev, kern_avg_ms = timed_block(True)
+        # untimed instrumented pass: per-state work counters of the same sweeps
+        restore()
+        ws.set_timing(False, count=True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        counters = ws.counters()
+        ws.set_timing(False)
     exh = None
-    if not args.no_extra and args.mode == 1 and world == 1:
+    if args.full and not args.no_extra and args.mode == 1 and world == 1:
         # SURVEY D3's exhaustive kernel (mode 2: table + plain scan + merge), same sweeps
         restore()
         exh_ms = []
@@ -359,11 +430,20 @@ def main():
         exh = sorted(exh_ms)[1]
         restore()
     if world > 1:
-        tt = torch.tensor([dt, kern_avg_ms], dtype=torch.float64, device=dev)
+        tt = torch.tensor([dt, kern_avg_ms or 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt, kern_avg_ms = float(tt[0]), float(tt[1])
+        dt = float(tt[0])
+        kern_avg_ms = float(tt[1]) if args.full else None
 
     progress(f"headline: {dt / args.steps * 1e3:.4f} ms/step")
+    if not args.full:   # the plain run ends here: the result line of the one timed block
+        if rank == 0:
+            import bench_report
+            out = headline(args, cal, world, r, w, dt, blocks)
+            print(bench_report.contract_line(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     legs = {}
     if not args.no_ks:   # BASELINE configs[4]: KS VFI sharded over the same ranks (strong)
         import bench_ks
@@ -384,7 +464,6 @@ def main():
         info = BL.cpu_info()
         threads = info["threads_all"]
         evals_per_sweep = N * Na * Na
-        value = world * evals_per_sweep * args.steps / dt
         feas = feasible_candidates(cal["a_grid"], cal["s"], r, w)
         tests = {n: c / args.steps for n, c in zip(("exact", "superblock", "block", "candidate"),
                                                    counters)}
@@ -400,44 +479,18 @@ def main():
         # PMC / HBM-traffic passes over the same sweeps 6..25 on the current kernels
         # (tools/exp/r06_pmc.sh: tools/pmc.sh + pmc_summary / pmc_traffic, skip 5 take 20)
         pmc_d, traffic, pmc_src = _counters("tree", "vfi_tree")
-        step_ms = sorted(blocks)
-        out = {
-            "metric": "Bellman evals/sec (Na·Na'·Nz, fp64)",
-            "value": value,
-            "unit": "evals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (reference calibration: Rouwenhorst Nz=7, quadratic grid)",
-            "config": {"workload": f"aiyagari_vfi_sweep Na={Na} Nz={N} rouwenhorst"
-                                   + (" (BASELINE configs[1])" if (Na, N) == (20000, 7) else ""),
-                       "Na": Na, "Nz": N, "sigma": cal["sigma"], "beta": cal["beta"],
-                       "search": "exhaustive over a' (exact bound-tree screen)" if args.mode == 1
-                                 else "exhaustive over a' (plain)",
-                       "sweeps_timed": f"sweeps {args.warmup + 1}..{args.warmup + args.steps} of a "
-                                       f"solve from v=0, hint = previous argmax",
-                       "parallelism": (f"replicas: one GE candidate r per rank ({world})"
-                                       if world > 1 and args.distinct_r else
-                                       f"replicas: the same sweeps (r = 0.04) on each of {world} "
-                                       f"rank(s), no data-path collective"),
-                       "feasible_fraction": feas / evals_per_sweep,
-                       "tests_per_sweep": tests},
-            "repeats": {"n": len(blocks), "median_ms_per_step": step_ms[len(blocks) // 2]
-                        / args.steps * 1e3, "min_ms_per_step": step_ms[0] / args.steps * 1e3,
-                        "max_ms_per_step": step_ms[-1] / args.steps * 1e3,
-                        "first_block_ms_per_step": blocks[0] / args.steps * 1e3,
-                        "kernel_timing_block_ms_per_step": dt_ev / args.steps * 1e3,
-                        "gpu_clock": BL.gpu_clock(local),
-                        "note": "the same sweeps re-run from a snapshot; value = the median block "
-                                "(SURVEY D7); "
-                                "the kernel average comes from one more block of the same sweeps "
-                                "with HIP events around every launch (their gaps excluded from "
-                                "the contract blocks)"},
+        out = headline(args, cal, world, r, w, dt, blocks)
+        out["config"].update(feasible_fraction=feas / evals_per_sweep, tests_per_sweep=tests)
+        out["repeats"].update({
+            "first_block_ms_per_step": blocks[0] / args.steps * 1e3,
+            "kernel_timing_block_ms_per_step": dt_ev / args.steps * 1e3,
+            "gpu_clock": BL.gpu_clock(local),
+            "note": "the same sweeps re-run from a snapshot; value = the median block "
+                    "(SURVEY D7); "
+                    "the kernel average comes from one more block of the same sweeps "
+                    "with HIP events around every launch (their gaps excluded from "
+                    "the contract blocks)"})
+        out.update({
             "roofline": {"bound": "valu", "achieved": achieved, "peak": PEAK_FP64_TFLOPS,
                          "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_TFLOPS,
                          "traffic": traffic,
@@ -456,7 +509,7 @@ def main():
                          "pmc_source": f"{pmc_src} (rocprofv3 --pmc, tools/pmc.sh + "
                                        f"tools/pmc_summary.py / pmc_traffic.py, same sweeps "
                                        f"6..25)"},
-        }
+        })
         out.update(legs)
         if exh is not None:  # the plain exhaustive scan's own roofline (mode 2)
             fl = FLOPS_PER_CANDIDATE * feas / (exh * 1e-3) / 1e12

@@ -13,6 +13,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -108,6 +109,40 @@ def test_side_benches_refuse_world_mismatch(script):
     r = subprocess.run([sys.executable, str(ROOT / script), "--gpus", "4"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr
+
+
+def test_plain_headline_line():
+    """The plain run's line: the contract fields of one timed block, none of the --full legs."""
+    import argparse
+    import bench
+    args = argparse.Namespace(steps=4, warmup=2, mode=1, distinct_r=False)
+    cal = {"N": 7, "Na": 1000, "sigma": 5.0, "beta": 0.96}
+    out = bench.headline(args, cal, 1, 0.04, 1.0, 2e-3, [2e-3])
+    c = json.loads(bench_report.contract_line(out))
+    assert c["steps"] == 4 and c["warmup"] == 2 and c["dtype"] == "f64"
+    assert c["ms_per_step"] == pytest.approx(0.5) and c["value"] == pytest.approx(7e6 * 4 / 2e-3)
+    assert c["unit"] == "evals/s" and c["higher_is_better"] is True and c["repeats"]["n"] == 1
+    assert not {"legs", "roofline", "cpu_baseline", "detail"} & set(c)
+
+
+def test_dump_outputs_float64_and_size_cap(tmp_path):
+    """--dump-outputs: float64 .npy, int32 indices exact; past 64 MB in all, the same seeded
+    sample of every array, identical from call to call."""
+    import torch
+    import bench
+    idx = torch.arange(12, dtype=torch.int32).reshape(3, 4)
+    v = torch.linspace(-1.0, 1.0, 12, dtype=torch.float64).reshape(3, 4)
+    bench.dump_outputs(tmp_path / "a", v_new=v, idx=idx)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"v_new", "idx"} and all(x.dtype == np.float64 for x in got.values())
+    assert np.array_equal(got["v_new"], v.numpy()) and np.array_equal(got["idx"], idx.numpy())
+    big = torch.arange(5 << 20, dtype=torch.float64)   # 2 x 40 MB > 64 MB: 4 Mi entries each
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, x=big, y=-big)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.size == y.size == 4 << 20 and (x.nbytes + y.nbytes) <= 64 << 20
+    assert np.array_equal(x, -y) and np.all(np.diff(x) > 0)
+    assert np.array_equal(x, np.load(tmp_path / "c" / "x.npy"))
 
 
 def test_failed_leg_is_reported():

@@ -7,7 +7,7 @@ cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 export TMPDIR=/tmp
 O=${O:-gpurun_out/ab}
 mkdir -p $O
-ARGS=${ARGS:---no-cpu-baseline --no-ks --no-ge --no-panel --no-extra}
+ARGS=${ARGS:---full --no-cpu-baseline --no-ks --no-ge --no-panel --no-extra}
 for rnd in $(seq 1 ${ROUNDS:-2}); do
   for L in $LIBS; do
     tag=$(basename $L .so)_$rnd

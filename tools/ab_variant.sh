@@ -6,7 +6,7 @@ cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}
 export TMPDIR=/tmp
 O=${O:-gpurun_out/abv}
 mkdir -p $O
-ARGS=${ARGS:---no-cpu-baseline --no-ks --no-ge --no-panel --no-extra}
+ARGS=${ARGS:---full --no-cpu-baseline --no-ks --no-ge --no-panel --no-extra}
 for rnd in $(seq 1 ${ROUNDS:-2}); do
   for V in $VARS; do
     tag=v${V}_$rnd

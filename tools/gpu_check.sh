@@ -22,9 +22,9 @@ for s in ${STEPS:-tests smoke bench prof}; do
     tests) if [ -n "$PYTEST_K" ]; then step pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -k "$PYTEST_K";
            else step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread; fi ;;
     smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python -u bench.py ${BENCH_ARGS} ;;
-    prof)  step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -o run -- python3 "$PWD/bench.py" --no-cpu-baseline --no-ge --no-solve ${BENCH_ARGS} ;;
-    pmc)   PMC_ARGS="--no-cpu-baseline --no-ge --no-solve --no-ks --steps 20 --warmup 5"
+    bench) step bench 600 python -u bench.py --full ${BENCH_ARGS} ;;
+    prof)  step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -o run -- python3 "$PWD/bench.py" --full --no-cpu-baseline --no-ge --no-solve ${BENCH_ARGS} ;;
+    pmc)   PMC_ARGS="--full --no-cpu-baseline --no-ge --no-solve --no-ks --steps 20 --warmup 5"
            step pmc_fetch 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$PWD/$OUT/pmc/fetch" -o run -- python3 "$PWD/bench.py" $PMC_ARGS
            step pmc_write 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$PWD/$OUT/pmc/write" -o run -- python3 "$PWD/bench.py" $PMC_ARGS
            python3 tools/pmc_traffic.py "$OUT/pmc" bell_tree_kernel "$OUT/traffic_vfi_tree.json" ;;

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-variants}
 mkdir -p "$OUT"
 for v in ${VARIANTS:-0 2 4 6 16 18 20}; do
-  timeout -k 10 120 python -u bench.py --na ${NA:-20000} --no-cpu-baseline --no-ge --no-ks --no-panel \
+  timeout -k 10 120 python -u bench.py --full --na ${NA:-20000} --no-cpu-baseline --no-ge --no-ks --no-panel \
       --steps 20 --warmup 5 --variant $v ${BENCH_EXTRA} > "$OUT/v$v.log" 2>&1 || exit $?
   python3 - "$OUT/v$v.log" $v <<'EOF'
 import json, sys
