@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <string>
 
@@ -34,6 +35,22 @@ int wait_event(hipEvent_t ev);
         int rc_ = (expr);            \
         if (rc_ != AIY_OK) return rc_; \
     } while (0)
+
+// A launch with more than 64 KiB of dynamic LDS needs the kernel's
+// hipFuncAttributeMaxDynamicSharedMemorySize raised first, and the attribute is per device.
+// Raises it to `bytes` (the most any call asks of K) once per (kernel instantiation K, current
+// device) — not per launch: that was measurable host time on the GE path.
+template <auto K>
+inline int raise_dynamic_lds(int bytes) {
+    static std::atomic<unsigned long long> done{0};  // bit d: device d has the limit
+    int dev = 0;
+    AIY_HIP(hipGetDevice(&dev));
+    const unsigned long long bit = (unsigned)dev < 64u ? 1ull << dev : 0ull;  // (else: every call)
+    if (done.load(std::memory_order_acquire) & bit) return AIY_OK;
+    AIY_HIP(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_release);
+    return AIY_OK;
+}
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ int readfirst(int x) { return __builtin_amdgcn_readfirstlane(x); }

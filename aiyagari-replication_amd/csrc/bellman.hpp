@@ -14,7 +14,7 @@ struct BellArgs {
     int np;          // sigma-1 when sigma is an integer in [2, 9]; 0 = generic sigma
     int coarse;      // init coarse stride S (0 = no coarse scan)
     int CK;          // candidates a' per work item
-    int variant;     // screen kernel geometry (tuning): bit0 R=4, bit1 register cap, bit2 fp64-only screen
+    int variant;     // kernel geometry and A/B knobs (tuning): the kVar* bits below
     double r, w, beta, sigma;
     const double* v_old;
     const double* a;
@@ -67,14 +67,76 @@ struct BellArgs {
     int parity;
 };
 
+// The workspace's variant word (aiy_ws_set_variant; the public legend is its comment in
+// include/aiyagari_hip.h).  Tuning and A/B only: results are identical for every value.
+// Bits 0-2 are read by geometry: the tree screen (kVarChunked clear) or the chunked screen.
+constexpr int kVarR2 = 1 << 0;           // tree: 2 states per lane (else 1)
+constexpr int kVarWavesShift = 1;        // tree, bits 1-2: 1, 2, 4 or 8 cooperating waves per tile
+constexpr int kVarWavesMask = 3 << kVarWavesShift;
+constexpr int kVarR4 = 1 << 0;           // chunked: 4 states per lane (else 2)
+constexpr int kVarRegCap = 1 << 1;       // chunked: registers capped for 8 waves per SIMD
+constexpr int kVarFp64Screen = 1 << 2;   // chunked: fp64-only screen (no packed fp32 pre-screen)
+constexpr int kVarChunked = 1 << 3;      // the chunked screen + merge instead of the bound tree
+constexpr int kVarXcdOrder = 1 << 4;     // XCD-aware tile order
+constexpr int kVarNoClimb = 1 << 5;      // no hill-climb from the hint
+constexpr int kVarPermHeavy = 1 << 6;    // dispatch permutation: each XCD's range heaviest first
+constexpr int kVarHintWinShift = 7;      // bits 7-8: hint window half-width 1, 2, 4 or 8
+constexpr int kVarHintWinMask = 3 << kVarHintWinShift;
+constexpr int kVarNoMomentum = 1 << 9;   // no extrapolated (hint + last shift) start
+constexpr int kVarExhaustive = 1 << 10;  // the plain exhaustive scan
+constexpr int kVarPermCheapLast = 1 << 11;  // dispatch permutation: row-major, cheapest tiles last
+constexpr int kVarDealBlocks = 1 << 12;  // cooperating waves deal the passing 8-blocks round-robin
+constexpr int kVarNarrowTiles = 1 << 13; // one-wave tiles narrowed to ceil(N·Na / 3072) states
+constexpr int kVarEvValu = 1 << 14;      // force the VALU expectation
+constexpr int kVarEvMfma = 1 << 15;      // force the MFMA expectation
+constexpr int kVarPackShift = 16;        // bits 16-17: 1, 2, 4 or 8 one-wave tiles per workgroup
+constexpr int kVarPackMask = 3 << kVarPackShift;
+// EGM A/B knobs, on bits of their own so that a VFI variant never changes the EGM path on a
+// shared workspace; read through egm_knob (ws.hpp)
+constexpr int kEgmTwoLaunch = 1 << 18;   // the two-launch step even for Na <= 1,024
+constexpr int kEgmNoChain = 1 << 19;     // solve loop: two launches per step, no chaining
+constexpr int kEgmNoHints = 1 << 20;     // interp1 without the previous step's segment windows
+constexpr int kVarDriftExtrap = 1 << 21; // start-up extrapolates the drift from the last two shifts
+constexpr int kVarHintAlone = 1 << 23;   // the hint's window is the hint alone when the
+                                         // extrapolated window is evaluated
+constexpr int kVarNoHintEval = 1 << 24;  // (with kVarHintAlone) not even the hint then
+constexpr int kVarWide = 1 << 25;        // the small-grid one-launch sweep with an explicit variant
+constexpr int kVarHybrid = 1 << 26;      // the hybrid tree launch (with a dispatch permutation)
+constexpr int kVarCoopShift = 27;        // bits 27-29: cooperative tiles per XCD range, 8 << value
+constexpr int kVarCoopMask = 7 << kVarCoopShift;
+// any cooperative / chunked geometry: not the one-state-per-lane, one-wave-per-tile tree
+constexpr int kVarGeometryMask = kVarR2 | kVarWavesMask | kVarChunked;
+// what the cached dispatch permutation depends on (with the tile width)
+constexpr int kVarPermKeyMask =
+    kVarPermHeavy | kVarPermCheapLast | kVarPackMask | kVarHybrid | kVarCoopMask;
+constexpr int kVarPermMask = kVarPermHeavy | kVarPermCheapLast;  // a dispatch permutation
+constexpr int kVarScreenGeoMask = kVarR4 | kVarRegCap;  // the chunked screen's instantiations
+constexpr int var_waves(int log2_waves) { return log2_waves << kVarWavesShift; }
+constexpr int var_pack(int log2_tiles) { return log2_tiles << kVarPackShift; }
+// the fields are disjoint (their sum is their union) and fit aiy_ws_set_variant's [0, 2^30)
+constexpr int kVarFields[] = {
+    kVarR2, kVarWavesMask, kVarChunked, kVarXcdOrder, kVarNoClimb, kVarPermHeavy, kVarHintWinMask,
+    kVarNoMomentum, kVarExhaustive, kVarPermCheapLast, kVarDealBlocks, kVarNarrowTiles, kVarEvValu,
+    kVarEvMfma, kVarPackMask, kEgmTwoLaunch, kEgmNoChain, kEgmNoHints, kVarDriftExtrap,
+    kVarHintAlone, kVarNoHintEval, kVarWide, kVarHybrid, kVarCoopMask};
+constexpr bool var_fields_disjoint() {
+    long long sum = 0, all = 0;
+    for (int f : kVarFields) sum += f, all |= f;
+    return sum == all && all < (1ll << 30);
+}
+static_assert(var_fields_disjoint(), "variant fields overlap");
+static_assert(kVarGeometryMask == (1 | 2 | 4 | 8) && (kVarRegCap | kVarFp64Screen) == kVarWavesMask,
+              "bits 0-3 are the geometry, read either as the tree's or as the chunked screen's");
+static_assert(kVarPermKeyMask == (64 | 2048 | (3 << 16) | (15 << 26)), "permutation cache key");
+
 // EV by fp64 MFMA from this productivity-grid size up (the variant bits 14 / 15 force VALU /
 // MFMA); below it the table kernel's sequential VALU sum, which the C oracle restates bit for
 // bit.  The MFMA's accumulation order is the hardware's: parity there is to rounding (MATLAB's
 // own BLAS order for beta*P*v_old is unpinned).
 constexpr int kEvMfmaMinN = 32;
 inline bool bell_ev_mfma(int N, int variant) {
-    if (variant >= 0 && (variant & 16384)) return false;
-    if (variant >= 0 && (variant & 32768)) return true;
+    if (variant >= 0 && (variant & kVarEvValu)) return false;
+    if (variant >= 0 && (variant & kVarEvMfma)) return true;
     return N >= kEvMfmaMinN;
 }
 // states per tree tile (R states per lane): 64·R, or A.tw for the one-state-per-lane geometry
@@ -83,17 +145,17 @@ inline int bell_tile_width(const BellArgs& A, int R) { return (R == 1 && A.tw > 
 // permutation (A.perm, which then holds -1 in the last workgroup's unused slots); instantiated
 // for A1 at sigma = 5 (np = 4), one state per lane, one wave per tile
 inline int bell_tree_pack(const BellArgs& A) {
-    if (!(A.np == 4 && !A.labor && A.tree && (A.variant & (1 | 2 | 4 | 8)) == 0)) return 1;
-    return (A.variant & (1 << 26)) ? 2 : 1 << ((A.variant >> 16) & 3);
+    if (!(A.np == 4 && !A.labor && A.tree && (A.variant & kVarGeometryMask) == 0)) return 1;
+    return (A.variant & kVarHybrid) ? 2 : 1 << ((A.variant & kVarPackMask) >> kVarPackShift);
 }
 // variant bit 26 (with a permutation): the hybrid launch, two-wave workgroups that run either
 // two one-wave tiles or one heavy tile on both waves; bits 27-29: cooperative tiles per XCD
 // range, 8 << value (7: none)
 inline bool bell_tree_hybrid(const BellArgs& A) {
-    return (A.variant & (1 << 26)) && bell_tree_pack(A) == 2;
+    return (A.variant & kVarHybrid) && bell_tree_pack(A) == 2;
 }
 inline int bell_tree_coop_per_xcd(const BellArgs& A) {
-    const int v = (A.variant >> 27) & 7;
+    const int v = (A.variant & kVarCoopMask) >> kVarCoopShift;
     return v == 7 ? 0 : 8 << v;  // (7: none — the hybrid launch's own cost, for A/B)
 }
 // The small-grid sweep (bellman_wide_kernels.hip): ONE launch per sweep, a workgroup of NW

@@ -291,7 +291,7 @@ int launch_bell_table_batch(const BellArgs& A, unsigned long long* slots, int sw
     dim3 grid((A.Na + kTableBlock - 1) / kTableBlock, A.C * A.N);
     bell_table_batch_kernel<<<grid, kTableBlock, 0, st>>>(
         A.N, A.Na, A.P, A.v_old, A.beta, A.np, A.a, A.EV, A.Dt, A.Dm8, A.Dm512, A.nb8, A.nb512,
-        slots, const_cast<int*>(A.stop), sweep, tol, A.ev_mfma, (A.variant & 16) != 0);
+        slots, const_cast<int*>(A.stop), sweep, tol, A.ev_mfma, (A.variant & kVarXcdOrder) != 0);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }
@@ -747,7 +747,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     const long long t_boot = (INS && A0.trace) ? (long long)wall_clock64() : 0;  // (instrumentation)
     const long long c_boot = (INS && A0.trace) ? (long long)__builtin_amdgcn_s_memtime() : 0;
     int item = A0.perm ? A0.perm[block_id]
-                       : ((A0.variant & 16) ? xcd_remap(block_id, nblocks) : block_id);
+                       : ((A0.variant & kVarXcdOrder) ? xcd_remap(block_id, nblocks) : block_id);
     if (PK > 1 && item < 0) return;  // (the last workgroup's unused slots)
     BellArgs A = A0;
     if (A0.C > 1) {  // batched candidates: blocks [c·N·ntile, (c+1)·N·ntile) are candidate c's
@@ -796,7 +796,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     // start-up also tries hint + shift — in the early sweeps of a solve the optimum drifts by
     // tens of candidates per sweep and a climb from the stale hint costs a dependent round
     // trip per step.  Only the screening bar depends on it, never the result.
-    int* __restrict__ mom = (A.variant & 512) ? nullptr : A.mom;
+    int* __restrict__ mom = (A.variant & kVarNoMomentum) ? nullptr : A.mom;
     unsigned nsu = 0;  // (instrumentation) the start-up's exact evaluations: window + climb
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -818,7 +818,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             const int mraw = (mom && h >= 0) ? mom[t] : 0;
             const int ms0 = (int)(short)(mraw & 0xffff), ms1 = (int)(short)(mraw >> 16);
             mlast[r] = ms0;
-            const int mv = max(-Na, min(Na, (A.variant & (1 << 21)) ? 2 * ms0 - ms1 : ms0));
+            const int mv = max(-Na, min(Na, (A.variant & kVarDriftExtrap) ? 2 * ms0 - ms1 : ms0));
             if (h >= 0) {
                 const int hl = h % Nl;
                 const int kf = A.kf[hl * nall + t];
@@ -835,7 +835,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     // variant bits 7-8), all loads in flight together, then their exact values
                     // (independent chains).  Indices are clamped into the feasible prefix; a
                     // repeated candidate merges as a no-op.
-                    const int wn = 1 << ((A.variant >> 7) & 3);
+                    const int wn = 1 << ((A.variant & kVarHintWinMask) >> kVarHintWinShift);
                     hk0[r] = hk;
                     // the extrapolated start hm = hint + last shift and its two neighbours,
                     // when that window does not touch the hint's own
@@ -844,10 +844,10 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     // hint alone (the drift predictor is usually right: three fewer evaluations)
                     constexpr int mw = 1;
                     const bool usem = hm > hk + wn + mw || hm < hk - wn - mw;
-                    const int wnh = (usem && (A.variant & (1 << 23))) ? 0 : wn;
+                    const int wnh = (usem && (A.variant & kVarHintAlone)) ? 0 : wn;
                     // bit 24 (with 23): not even the hint itself — the extrapolated window
                     // and the climb from it carry the start alone
-                    const bool skiph = usem && (A.variant & (1 << 24));
+                    const bool skiph = usem && (A.variant & kVarNoHintEval);
                     constexpr int WM = 8;
                     double wa[2 * WM + 1], we[2 * WM + 1], ma[3], me[3];
 #pragma unroll
@@ -893,7 +893,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     int dir = kb >= hk + wnh ? 1 : (kb <= hk - wnh ? -1 : 0);
                     if (usem && kb >= hm - mw && kb <= hm + mw)  // best in the extrapolated window
                         dir = kb == hm + mw ? 1 : (kb == hm - mw ? -1 : 0);
-                    if (dir != 0 && !(A.variant & 32)) {
+                    if (dir != 0 && !(A.variant & kVarNoClimb)) {
                         int k = kb, step = 2;
                         for (;;) {
                             const int kn = min(max(k + dir * step, 0), kf - 1);
@@ -1267,7 +1267,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             double d8, a8;
             load8(sfirst, d8, a8);
             const unsigned long long p = prep(sfirst, wave, W, d8, a8, st_cur,
-                                              (A.variant & 4096) != 0);
+                                              (A.variant & kVarDealBlocks) != 0);
             if (p) finish(sfirst, p, st_cur);
             exchange();
             set_B();
@@ -1632,7 +1632,7 @@ int launch_bell_table(const BellArgs& A, hipStream_t st) {
         A.N, A.Na, A.P, A.v_old, A.beta, A.np, A.a, A.EV, (scr && !A.tree) ? A.T : nullptr,
         scr ? A.T32 : nullptr, A.CK, scr ? A.Dm : nullptr, scr ? A.Dm8 : nullptr,
         scr ? A.Dm512 : nullptr, A.nb, A.nb8, A.nb512, A.diff, scr ? A.Dt : nullptr, A.fold,
-        A.ev_mfma, (A.variant & 16) != 0);
+        A.ev_mfma, (A.variant & kVarXcdOrder) != 0);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }
@@ -1689,10 +1689,10 @@ static void run_screen(const BellArgs& A, hipStream_t st) {
             screen_geo<NP, LAB, 1, 1>(A, st);
         } else {
             // variant: bit 0 → 4 states per lane (else 2); bit 1 → cap registers for 8 waves/SIMD
-            switch (A.variant & 3) {
-                case 1: screen_geo<NP, LAB, 4, 1>(A, st); break;
-                case 2: screen_geo<NP, LAB, 2, 8>(A, st); break;
-                case 3: screen_geo<NP, LAB, 4, 8>(A, st); break;
+            switch (A.variant & kVarScreenGeoMask) {
+                case kVarR4: screen_geo<NP, LAB, 4, 1>(A, st); break;
+                case kVarRegCap: screen_geo<NP, LAB, 2, 8>(A, st); break;
+                case kVarR4 | kVarRegCap: screen_geo<NP, LAB, 4, 8>(A, st); break;
                 default: screen_geo<NP, LAB, 2, 1>(A, st); break;
             }
         }
@@ -1714,10 +1714,10 @@ static void tree_geo(const BellArgs& A, hipStream_t st) {
 // one-wave tiles with a dispatch permutation: bell_tree_pack waves per workgroup
 template <int NP, bool LAB, int R>
 static void tree_w(const BellArgs& A, hipStream_t st) {
-    switch ((A.variant >> 1) & 3) {
-        case 1: tree_geo<NP, LAB, R, 2>(A, st); break;
-        case 2: tree_geo<NP, LAB, R, 4>(A, st); break;
-        case 3: tree_geo<NP, LAB, R, 8>(A, st); break;
+    switch (A.variant & kVarWavesMask) {
+        case var_waves(1): tree_geo<NP, LAB, R, 2>(A, st); break;
+        case var_waves(2): tree_geo<NP, LAB, R, 4>(A, st); break;
+        case var_waves(3): tree_geo<NP, LAB, R, 8>(A, st); break;
         default:
             if constexpr (!LAB && R == 1) {
                 if (A.perm && bell_tree_hybrid(A)) {
@@ -1747,7 +1747,7 @@ static void run_tree(const BellArgs& A, hipStream_t st) {
     if constexpr (NP > 0) {
         // the tuning geometries are instantiated for the reference sigma = 5 (NP = 4) only
         if constexpr (!LAB && NP == 4) {
-            if (A.variant & 1) tree_w<NP, LAB, 2>(A, st);
+            if (A.variant & kVarR2) tree_w<NP, LAB, 2>(A, st);
             else tree_w<NP, LAB, 1>(A, st);
         } else if constexpr (LAB && NP == 4) {  // labour: cooperating waves per tile (bits 1-2)
             tree_w<NP, LAB, 1>(A, st);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "aiy_common.hpp"
+#include "tree_perm.hpp"
 #include "ws.hpp"
 
 namespace aiy {
@@ -51,55 +52,38 @@ int fail(int code, const char* fmt, ...) {
 }
 
 // ---------------------------------------------------------------------------- workspace
-template <class T>
-static int dalloc(T** p, size_t n) {
-    if (*p) return AIY_OK;
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess)
-        return fail(AIY_NO_MEMORY, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T),
-                    hipGetErrorString(e));
-    return AIY_OK;
+int ws_ensure_diff(aiy_ws* ws) {
+    AIY_TRY(ws->diff.ensure(2 * kDiffSlots));
+    return ws->hdiff.ensure(2 * kDiffSlots + 4);
 }
-template <class T>
-static void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
+
+int ws_ensure_trace(aiy_ws* ws, int64_t units, bool* fresh) {
+    return ws->trace.ensure(16 * (size_t)units, fresh);
 }
 
 int ws_ensure_bell(aiy_ws* ws, size_t partial_slots) {
-    size_t n = (size_t)ws->N * ws->Na;
-    AIY_TRY(dalloc(&ws->EV, n));
-    AIY_TRY(dalloc(&ws->T, n));
-    AIY_TRY(dalloc(&ws->T32, 2 * (size_t)ws->N * (ws->Na + (ws->Na & 1))));
-    AIY_TRY(dalloc(&ws->Dm, (size_t)ws->N * ((ws->Na + 63) / 64)));
-    AIY_TRY(dalloc(&ws->Dm8, (size_t)ws->N * ((ws->Na + 7) / 8)));
-    AIY_TRY(dalloc(&ws->Dt, n));
-    AIY_TRY(dalloc(&ws->Dm512, (size_t)ws->N * ((ws->Na + 511) / 512)));
-    AIY_TRY(dalloc(&ws->best0, n));
-    AIY_TRY(dalloc(&ws->idx0, n));
-    if (!ws->mom) {
-        AIY_TRY(dalloc(&ws->mom, n));
-        AIY_HIP(hipMemset(ws->mom, 0, n * sizeof(int)));
-    }
-    if (!ws->touched) {  // the merge kernel leaves touched = 0 and partial = -1 behind
-        AIY_TRY(dalloc(&ws->touched, n));
-        AIY_HIP(hipMemset(ws->touched, 0, n * sizeof(int)));
-    }
-    if (ws->partial && ws->partial_cap < partial_slots) dfree(ws->partial);
-    if (!ws->partial) {
-        AIY_TRY(dalloc(&ws->partial, partial_slots));
-        AIY_HIP(hipMemset(ws->partial, 0xff, partial_slots * sizeof(int)));
-        ws->partial_cap = partial_slots;
-    }
-    AIY_TRY(dalloc(&ws->diff, 2 * kDiffSlots));
-    if (!ws->hitcount) {  // zero from the start: counting may be switched on before a sweep
-        AIY_TRY(dalloc(&ws->hitcount, 4 * kDiffSlots));
+    const size_t n = (size_t)ws->N * ws->Na;
+    bool fresh;
+    AIY_TRY(ws->EV.ensure(n));
+    AIY_TRY(ws->T.ensure(n));
+    AIY_TRY(ws->T32.ensure(2 * (size_t)ws->N * (ws->Na + (ws->Na & 1))));
+    AIY_TRY(ws->Dm.ensure((size_t)ws->N * ((ws->Na + 63) / 64)));
+    AIY_TRY(ws->Dm8.ensure((size_t)ws->N * ((ws->Na + 7) / 8)));
+    AIY_TRY(ws->Dt.ensure(n));
+    AIY_TRY(ws->Dm512.ensure((size_t)ws->N * ((ws->Na + 511) / 512)));
+    AIY_TRY(ws->best0.ensure(n));
+    AIY_TRY(ws->idx0.ensure(n));
+    AIY_TRY(ws->mom.ensure(n, &fresh));
+    if (fresh) AIY_HIP(hipMemset(ws->mom, 0, n * sizeof(int)));
+    AIY_TRY(ws->touched.ensure(n, &fresh));  // the merge kernel leaves touched = 0 and
+    if (fresh) AIY_HIP(hipMemset(ws->touched, 0, n * sizeof(int)));  // partial = -1 behind
+    AIY_TRY(ws->partial.ensure(partial_slots, &fresh));
+    if (fresh) AIY_HIP(hipMemset(ws->partial, 0xff, partial_slots * sizeof(int)));
+    AIY_TRY(ws_ensure_diff(ws));  // (here: the device allocations keep the order they always had)
+    AIY_TRY(ws->hitcount.ensure(4 * kDiffSlots, &fresh));
+    if (fresh)  // zero from the start: counting may be switched on before a sweep
         AIY_HIP(hipMemset(ws->hitcount, 0, 4 * kDiffSlots * sizeof(unsigned long long)));
-    }
-    AIY_TRY(dalloc(&ws->dis, (size_t)std::max<int64_t>(ws->Nl, 1)));
-    if (!ws->hdiff)
-        AIY_HIP(hipHostMalloc((void**)&ws->hdiff, (2 * kDiffSlots + 4) * sizeof(unsigned long long)));
-    return AIY_OK;
+    return ws->dis.ensure((size_t)std::max<int64_t>(ws->Nl, 1));
 }
 
 int ws_timing_begin(aiy_ws* ws, hipStream_t st) {
@@ -181,16 +165,17 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
     // extrapolated window is used) on top for A1: 36.2 -> 35.75 us (profiles/r04_g33_*); bit 24
     // (no hint evaluation then at all): kernel 30.9 -> 30.6 us, step 35.7 -> 35.6 (r04_g36_*)
     const int var = ws->variant >= 0 ? ws->variant
-                    : ws->Na <= 4096 ? (c.labor ? 4 | 4096 : 2)
-                    : (c.labor ? 16 | 1 << 21
-                               : 16 | 2048 | 1 << 16 | 1 << 21 | 1 << 23 | 1 << 24);
+                    : ws->Na <= 4096 ? (c.labor ? var_waves(2) | kVarDealBlocks : var_waves(1))
+                    : (c.labor ? kVarXcdOrder | kVarDriftExtrap
+                               : kVarXcdOrder | kVarPermCheapLast | var_pack(1) | kVarDriftExtrap |
+                                     kVarHintAlone | kVarNoHintEval);
     A.variant = var;
     A.ev_mfma = bell_ev_mfma(A.N, ws->variant);
     // (variant bit 13) one-wave tiles of tw < 64 states, tw = ceil(N·Na / (3 waves × 1,024
     // SIMDs)): every SIMD holds three tiles instead of two or three (the 3-wave SIMDs end the
     // launch, tools/tree_trace.py); lanes tw..63 idle.  Work split only.
     A.tw = 0;
-    if ((var & 8192) && !c.labor && (var & (1 | 2 | 4 | 8)) == 0) {
+    if ((var & kVarNarrowTiles) && !c.labor && (var & kVarGeometryMask) == 0) {
         const int64_t tw = (ws->N * ws->Na + 3 * 1024 - 1) / (3 * 1024);
         A.tw = (int)std::max<int64_t>(16, std::min<int64_t>(64, tw));
         if (A.tw == 64) A.tw = 0;
@@ -209,8 +194,8 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
     A.dis = c.labor ? ws->dis : nullptr;
     A.EV = ws->EV;
     A.T = ws->T;
-    A.tree = (var & 8) == 0;
-    A.T32 = (A.tree || (var & 4)) ? nullptr : ws->T32;
+    A.tree = (var & kVarChunked) == 0;
+    A.T32 = (A.tree || (var & kVarFp64Screen)) ? nullptr : ws->T32;
     A.Dm = A.tree ? nullptr : ws->Dm;
     A.Dm8 = A.tree ? ws->Dm8 : nullptr;
     A.Dt = A.tree ? ws->Dt : nullptr;
@@ -226,13 +211,9 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
     A.hitcount = ws->count_hits ? ws->hitcount : nullptr;
     A.trace = nullptr;
     if (ws->tracing) {
-        const int64_t cap = (int64_t)ws->N * ((ws->Na + 15) / 16);  // quad tiles: 16 states
-        if (ws->trace_cap < cap) {
-            dfree(ws->trace);
-            AIY_TRY(dalloc(&ws->trace, 16 * (size_t)cap));
-            AIY_HIP(hipMemset(ws->trace, 0, 16 * (size_t)cap * sizeof(long long)));
-            ws->trace_cap = cap;
-        }
+        bool fresh;  // a record per quad tile: 16 states
+        AIY_TRY(ws_ensure_trace(ws, (int64_t)ws->N * ((ws->Na + 15) / 16), &fresh));
+        if (fresh) AIY_HIP(hipMemset(ws->trace, 0, ws->trace.cap() * sizeof(long long)));
         A.trace = ws->trace;
     }
     A.v_new = c.v_new;
@@ -251,16 +232,9 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
         ws->dis_L = c.L; ws->dis_Nl = c.Nl; ws->dis_psi = c.psi; ws->dis_eta = c.eta;
     }
     // feasible prefixes: cached while (r, w, a, s, L) are unchanged (aiy_ws_invalidate resets)
-    size_t kf_need = (size_t)A.Nl * A.N * A.Na;
-    if (ws->kf && ws->kf_cap < kf_need) {
-        (void)hipFree(ws->kf);
-        ws->kf = nullptr;
-        ws->kf_ok = false;
-    }
-    if (!ws->kf) {
-        AIY_HIP(hipMalloc((void**)&ws->kf, kf_need * sizeof(int)));
-        ws->kf_cap = kf_need;
-    }
+    bool kf_new;
+    AIY_TRY(ws->kf.ensure((size_t)A.Nl * A.N * A.Na, &kf_new));
+    if (kf_new) ws->kf_ok = false;
     A.kf = ws->kf;
     bool fresh = ws->kf_ok && ws->kf_r == c.r && ws->kf_w == c.w && ws->kf_a == c.a &&
                  ws->kf_s == c.s && ws->kf_L == A.L && ws->kf_Nl == A.Nl && ws->kf_lab == A.labor;
@@ -275,7 +249,7 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
     A.perm_slots = 0;
     if (tree_perm_eligible(A)) {
         const long long key = (long long)A.tw * (1ll << 31) +
-                              (A.variant & (64 | 2048 | (3 << 16) | (15 << 26)));
+                              (A.variant & kVarPermKeyMask);
         if (!ws->perm_ok || ws->perm_key != key) {
             AIY_TRY(ws_tree_perm(ws, A, st));
             ws->perm_key = key;
@@ -286,156 +260,37 @@ static int bell_args(aiy_ws* ws, const BellCall& c, BellArgs& A, hipStream_t st)
     return AIY_OK;
 }
 
-// Dispatch order of the one-wave-per-tile A1 tree launch (variant bit 6).  A launch of N·ntile
-// one-wave items on 1,024 SIMDs puts three waves on some SIMDs — the last-dispatched items of
-// each XCD — and those items end the launch (tools/tree_trace.py: every last-to-finish item sits
-// on a 3-wave SIMD).  The order keeps each XCD's item range (xcd_remap: the same L2 sets) and
-// deals it heaviest first, by the feasible prefix of the tile's last state (the bound tree's
-// superblock count), so the third waves are the cheapest tiles.  Work order only.
+// The dispatch permutation of the one-wave-per-tile A1 tree launch: the order is tree_perm.hpp's
+// (a pure function of the tiles' costs); here the costs are fetched and the order uploaded.
 bool tree_perm_eligible(const BellArgs& A) {
-    return (A.variant & (64 | 2048)) && A.tree && A.C <= 1 && A.np >= 1 && A.np <= 8 &&
-           (A.variant & (1 | 2 | 4 | 8)) == 0;
+    return (A.variant & kVarPermMask) && A.tree && A.C <= 1 && A.np >= 1 && A.np <= 8 &&
+           (A.variant & kVarGeometryMask) == 0;
 }
-constexpr int kSimdsPerXcd = 128;  // MI355X: 32 CUs x 4 SIMDs per XCD
-static int ws_tree_perm_hybrid(aiy_ws* ws, const BellArgs& A, const std::vector<int>& kl,
-                               int ntile, hipStream_t st);
+static int ws_upload_perm(aiy_ws* ws, const std::vector<int>& perm, hipStream_t st) {
+    AIY_TRY(ws->tree_perm.ensure(perm.size()));
+    AIY_HIP(hipMemcpyAsync(ws->tree_perm, perm.data(), perm.size() * sizeof(int),
+                           hipMemcpyHostToDevice, st));
+    AIY_HIP(hipStreamSynchronize(st));
+    ws->perm_ok = true;
+    ws->perm_slots = (int)perm.size();
+    return AIY_OK;
+}
 int ws_tree_perm(aiy_ws* ws, const BellArgs& A, hipStream_t st) {
     const int N = A.N, Na = A.Na, TW = bell_tile_width(A, 1), ntile = (Na + TW - 1) / TW;
-    const int G = N * ntile;
-    // PK one-wave tiles per workgroup (bell_tree_pack); workgroup b runs on XCD b mod 8, its
-    // waves take slots b·PK .. b·PK + PK - 1; the last workgroup's unused slots hold -1
-    const int PK = bell_tree_pack(A), nwg = (G + PK - 1) / PK, slots = nwg * PK;
     // only each tile's last state's prefixes cross to the host (not all of kf)
     const int rows = A.Nl * N;
-    if (ws->kf_last_cap < rows * ntile) {
-        if (ws->kf_last) (void)hipFree(ws->kf_last);
-        ws->kf_last = nullptr;
-        ws->kf_last_cap = 0;
-        AIY_HIP(hipMalloc((void**)&ws->kf_last, (size_t)rows * ntile * sizeof(int)));
-        ws->kf_last_cap = rows * ntile;
-    }
+    AIY_TRY(ws->kf_last.ensure((size_t)rows * ntile));
     std::vector<int> kl((size_t)rows * ntile);  // [labour level][row][tile]
     AIY_TRY(launch_kf_tile_last(A.kf, rows, Na, TW, ntile, ws->kf_last, st));
     AIY_HIP(hipMemcpyAsync(kl.data(), ws->kf_last, kl.size() * sizeof(int),
                            hipMemcpyDeviceToHost, st));
     AIY_HIP(hipStreamSynchronize(st));
-    if (bell_tree_hybrid(A)) return ws_tree_perm_hybrid(ws, A, kl, ntile, st);
-    std::vector<int> perm(slots, -1);
-    int start = 0;
-    for (int x = 0; x < 8; ++x) {
-        int size = (nwg / 8 + (x < nwg % 8 ? 1 : 0)) * PK;
-        if (x == (nwg - 1) % 8) size -= slots - G;
-        std::vector<int> items(size);
-        for (int u = 0; u < size; ++u) items[u] = start + u;
-        auto cost = [&](int it) {  // the feasible prefixes of the tile's last state
-            const int i = it / ntile, t = it % ntile;
-            long long c = 0;
-            for (int l = 0; l < A.Nl; ++l) c += kl[((size_t)l * N + i) * ntile + t];
-            return c;
-        };
-        if (A.variant & 64) {  // the whole range heaviest first
-            std::stable_sort(items.begin(), items.end(),
-                             [&](int a, int b) { return cost(a) > cost(b); });
-        } else {  // (bit 11) row-major, but the range's cheapest tiles dispatched last
-            const int tail = std::max(0, std::min(size, size - 2 * kSimdsPerXcd));
-            std::vector<int> by(items);
-            std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return cost(a) < cost(b); });
-            std::vector<char> last(G, 0);
-            for (int u = 0; u < tail; ++u) last[by[u]] = 1;
-            std::vector<int> out;
-            for (int it : items)
-                if (!last[it]) out.push_back(it);
-            for (int u = tail - 1; u >= 0; --u) out.push_back(by[u]);
-            items.swap(out);
-        }
-        for (int u = 0; u < size; ++u)  // the XCD's (u / PK)-th workgroup b = 8(u / PK) + x
-            perm[(size_t)(8 * (u / PK) + x) * PK + u % PK] = items[u];
-        start += size;
-    }
-    if (!ws->tree_perm || ws->perm_cap < slots) {
-        if (ws->tree_perm) (void)hipFree(ws->tree_perm);
-        ws->tree_perm = nullptr;
-        AIY_HIP(hipMalloc((void**)&ws->tree_perm, (size_t)slots * sizeof(int)));
-        ws->perm_cap = slots;
-    }
-    AIY_HIP(hipMemcpyAsync(ws->tree_perm, perm.data(), (size_t)slots * sizeof(int),
-                           hipMemcpyHostToDevice, st));
-    AIY_HIP(hipStreamSynchronize(st));
-    ws->perm_ok = true;
-    ws->perm_slots = slots;
-    return AIY_OK;
-}
-
-// The hybrid launch's order (variant bit 26): each XCD keeps its contiguous row-major range as
-// above; its H heaviest tiles (bits 27-29) become cooperative workgroups (slots {item, -2}),
-// dealt first, heaviest first; the rest are packed two per workgroup in row-major order with
-// the range's cheapest tiles last (the third waves on a SIMD).  Workgroup b runs on XCD b mod 8.
-static int ws_tree_perm_hybrid(aiy_ws* ws, const BellArgs& A, const std::vector<int>& kl,
-                               int ntile, hipStream_t st) {
-    const int N = A.N, G = N * ntile;
-    auto cost = [&](int it) {
-        const int i = it / ntile, t = it % ntile;
-        long long c = 0;
-        for (int l = 0; l < A.Nl; ++l) c += kl[((size_t)l * N + i) * ntile + t];
-        return c;
-    };
-    // split the items into 8 contiguous ranges, then each range into workgroups
-    std::vector<std::vector<int>> wg[8];  // per XCD: its workgroups' slot pairs, in order
-    int start = 0;
-    for (int x = 0; x < 8; ++x) {
-        const int size = G / 8 + (x < G % 8 ? 1 : 0);
-        std::vector<int> items(size);
-        for (int u = 0; u < size; ++u) items[u] = start + u;
-        start += size;
-        std::vector<int> by(items);
-        std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return cost(a) > cost(b); });
-        const int H = std::min(size, bell_tree_coop_per_xcd(A));
-        std::vector<char> coop(G, 0);
-        for (int u = 0; u < H; ++u) {
-            coop[by[u]] = 1;
-            wg[x].push_back({by[u], -2});
-        }
-        std::vector<int> rest;
-        for (int it : items)
-            if (!coop[it]) rest.push_back(it);
-        // the cheapest (size - H) - 2·128 one-wave tiles last, cheapest at the very end
-        const int R = (int)rest.size();
-        const int tail = std::max(0, R - 2 * kSimdsPerXcd);
-        std::vector<int> rb(rest);
-        std::stable_sort(rb.begin(), rb.end(), [&](int a, int b) { return cost(a) < cost(b); });
-        std::vector<char> last(G, 0);
-        for (int u = 0; u < tail; ++u) last[rb[u]] = 1;
-        std::vector<int> out;
-        for (int it : rest)
-            if (!last[it]) out.push_back(it);
-        for (int u = tail - 1; u >= 0; --u) out.push_back(rb[u]);
-        for (size_t u = 0; u < out.size(); u += 2)
-            wg[x].push_back({out[u], u + 1 < out.size() ? out[u + 1] : -1});
-    }
-    // interleave: workgroup b = 8q + x is XCD x's q-th; XCDs with fewer workgroups get empty
-    // ({-1, -1}) ones so that b mod 8 still names the XCD
-    size_t nq = 0;
-    for (int x = 0; x < 8; ++x) nq = std::max(nq, wg[x].size());
-    const int slots = (int)(8 * nq * 2);
-    std::vector<int> perm(slots, -1);
-    for (size_t q = 0; q < nq; ++q)
-        for (int x = 0; x < 8; ++x)
-            if (q < wg[x].size()) {
-                perm[(8 * q + x) * 2] = wg[x][q][0];
-                perm[(8 * q + x) * 2 + 1] = wg[x][q][1];
-            }
-    if (!ws->tree_perm || ws->perm_cap < slots) {
-        if (ws->tree_perm) (void)hipFree(ws->tree_perm);
-        ws->tree_perm = nullptr;
-        AIY_HIP(hipMalloc((void**)&ws->tree_perm, (size_t)slots * sizeof(int)));
-        ws->perm_cap = slots;
-    }
-    AIY_HIP(hipMemcpyAsync(ws->tree_perm, perm.data(), (size_t)slots * sizeof(int),
-                           hipMemcpyHostToDevice, st));
-    AIY_HIP(hipStreamSynchronize(st));
-    ws->perm_ok = true;
-    ws->perm_slots = slots;
-    return AIY_OK;
+    return ws_upload_perm(ws,
+                          bell_tree_hybrid(A)
+                              ? tree_perm_hybrid_order(kl, N, ntile, A.Nl, bell_tree_coop_per_xcd(A))
+                              : tree_perm_order(kl, N, ntile, A.Nl, bell_tree_pack(A),
+                                                (A.variant & kVarPermHeavy) != 0),
+                          st);
 }
 
 // The small-grid one-launch sweep (bellman_wide_kernels.hip) and its geometry.  Default: every
@@ -450,7 +305,7 @@ static bool wide_pick(const aiy_ws* ws, const BellArgs& A, int* S, int* NW, int*
     if (A.np < 1 || A.np > 8 || A.C > 1 || A.ev_mfma || A.Nl > kWideMaxNl) return false;
     const int vmax = ws->wide_max >= 0 ? ws->wide_max : (A.labor ? 2048 : 1536);
     if (A.Na > vmax) return false;
-    if (ws->variant >= 0 && !(ws->variant & (1 << 25))) return false;
+    if (ws->variant >= 0 && !(ws->variant & kVarWide)) return false;
     // states per wave: labour 16 up to Na = 512, then 32 (profiles/r05_wide_ab.txt, r05_g52:
     // Na = 1,000 30.8 -> 21.8 us, 2,000 69.9 -> 56.4); A1 32 up to 1,024, then 64
     const int sb = ws->wide_SB > 0 ? ws->wide_SB
@@ -467,23 +322,15 @@ static bool wide_pick(const aiy_ws* ws, const BellArgs& A, int* S, int* NW, int*
 static int bell_sweep_wide(aiy_ws* ws, BellArgs& A, int S, int NW, int SB, hipStream_t st) {
     const int ntile = (int)((ws->Na + SB - 1) / SB);
     const size_t items = (size_t)ws->N * ntile;
-    if (!ws->wdiff) {
-        AIY_TRY(dalloc(&ws->wdiff, 4 * (size_t)kDiffSlots));
+    bool fresh;
+    AIY_TRY(ws->wdiff.ensure(4 * (size_t)kDiffSlots, &fresh));
+    if (fresh) {
         AIY_HIP(hipMemsetAsync(ws->wdiff, 0, 4 * kDiffSlots * sizeof(unsigned long long), st));
         ws->wcur = 0;
     }
-    if (ws->wcnt_cap < items) {
-        dfree(ws->wcnt);
-        AIY_TRY(dalloc(&ws->wcnt, items));
-        AIY_HIP(hipMemsetAsync(ws->wcnt, 0, items * sizeof(unsigned), st));
-        ws->wcnt_cap = items;
-    }
-    const size_t pneed = items * (size_t)S * 64 * 2;
-    if (S > 1 && ws->wpart_cap < pneed) {
-        dfree(ws->wpart);
-        AIY_TRY(dalloc(&ws->wpart, pneed));
-        ws->wpart_cap = pneed;
-    }
+    AIY_TRY(ws->wcnt.ensure(items, &fresh));
+    if (fresh) AIY_HIP(hipMemsetAsync(ws->wcnt, 0, items * sizeof(unsigned), st));
+    if (S > 1) AIY_TRY(ws->wpart.ensure(items * (size_t)S * 64 * 2));
     unsigned long long* cur = ws->wdiff + (size_t)ws->wcur * 2 * kDiffSlots;
     unsigned long long* nxt = ws->wdiff + (size_t)(ws->wcur ^ 1) * 2 * kDiffSlots;
     if (A.fold && !ws->last_wide) {  // the previous sweep's slots are the table path's
@@ -493,13 +340,8 @@ static int bell_sweep_wide(aiy_ws* ws, BellArgs& A, int S, int NW, int SB, hipSt
     A.diff = nxt;  // zero (the set not current); block 0 folds and clears `cur`
     A.trace = nullptr;
     if (ws->tracing) {  // one 64-word record per block (instrumentation)
-        const int64_t blocks = ((int64_t)items + 7) / 8 * 8 * S * 4;  // (in 16-word units)
-        if (ws->trace_cap < blocks) {
-            dfree(ws->trace);
-            AIY_TRY(dalloc(&ws->trace, 16 * (size_t)blocks));
-            ws->trace_cap = blocks;
-        }
-        AIY_HIP(hipMemsetAsync(ws->trace, 0, 16 * (size_t)ws->trace_cap * sizeof(long long), st));
+        AIY_TRY(ws_ensure_trace(ws, ((int64_t)items + 7) / 8 * 8 * S * 4));  // (16-word units)
+        AIY_HIP(hipMemsetAsync(ws->trace, 0, ws->trace.cap() * sizeof(long long), st));
         A.trace = ws->trace;
     }
     const char* fl = getenv("AIY_WIDE_FLAGS");  // (A/B tooling: tools/wide_tune.py)
@@ -519,7 +361,7 @@ int bell_sweep_dev(aiy_ws* ws, const BellCall& c, hipStream_t st) {
     AIY_TRY(bell_args(ws, c, A, st));
     // mode 2 / variant bit 10: the exhaustive scan (one launch after the table, outputs written
     // by the scan itself); otherwise the bound tree (or the chunked screen, variant bit 3)
-    const bool exhaustive = c.mode == 2 || A.np == 0 || (A.variant & 1024);
+    const bool exhaustive = c.mode == 2 || A.np == 0 || (A.variant & kVarExhaustive);
     const bool screened = !exhaustive;
     int wS = 0, wNW = 0, wSB = 0;
     if (screened && wide_pick(ws, A, &wS, &wNW, &wSB)) {  // small grids: one launch per sweep
@@ -583,22 +425,22 @@ static int bell_solve_spec(aiy_ws* ws, BellCall c, double* v_a, double* v_b, dou
     // survive the next batch), idx / policies 2M, diff pairs 2M (indexed by sweep)
     const int M = ws->spec_max, R = 2 * M + 1, Rp = 2 * M, D = 2 * M;
     const size_t n = (size_t)ws->N * ws->Na;
-    if (ws->spec_n != n || ws->spec_m != M) {
-        ws->free_spec();
-        AIY_TRY(dalloc(&ws->spec_v, (size_t)R * n));
-        AIY_TRY(dalloc(&ws->spec_idx, (size_t)Rp * n));
-        AIY_TRY(dalloc(&ws->spec_pol, (size_t)Rp * 3 * n));
-        AIY_TRY(dalloc(&ws->spec_diff, 2 * (size_t)D));
-        AIY_HIP(hipHostMalloc((void**)&ws->spec_hdiff, 2 * 2 * (size_t)D * sizeof(unsigned long long)));
-        for (int b = 0; b < 2; ++b)
-            AIY_HIP(hipEventCreateWithFlags(&ws->spec_ev[b], hipEventDisableTiming));
-        ws->spec_n = n;
-        ws->spec_m = M;
+    SpecRings& sp = ws->spec;
+    if (sp.n != n || sp.m != M) {
+        sp = SpecRings{};
+        AIY_TRY(sp.v.ensure((size_t)R * n));
+        AIY_TRY(sp.idx.ensure((size_t)Rp * n));
+        AIY_TRY(sp.pol.ensure((size_t)Rp * 3 * n));
+        AIY_TRY(sp.diff.ensure(2 * (size_t)D));
+        AIY_TRY(sp.hdiff.ensure(2 * 2 * (size_t)D));
+        AIY_TRY(sp.ev.create(2, hipEventDisableTiming));
+        sp.n = n;
+        sp.m = M;
     }
-    auto vslot = [&](int64_t g) { return ws->spec_v + (size_t)(g % R) * n; };
-    auto islot = [&](int64_t g) { return ws->spec_idx + (size_t)(g % Rp) * n; };
-    auto pslot = [&](int64_t g, int q) { return ws->spec_pol + ((size_t)(g % Rp) * 3 + q) * n; };
-    auto dslot = [&](int64_t g) { return ws->spec_diff + 2 * (size_t)(g % D); };
+    auto vslot = [&](int64_t g) { return sp.v + (size_t)(g % R) * n; };
+    auto islot = [&](int64_t g) { return sp.idx + (size_t)(g % Rp) * n; };
+    auto pslot = [&](int64_t g, int q) { return sp.pol + ((size_t)(g % Rp) * 3 + q) * n; };
+    auto dslot = [&](int64_t g) { return sp.diff + 2 * (size_t)(g % D); };
     const size_t vb = n * sizeof(double);
     // slot 0 = v_old of sweep 1; slot 1 = the incoming v_new buffer (the labour sweep's
     // keep-incoming rule reads it on sweep 1)
@@ -615,12 +457,12 @@ static int bell_solve_spec(aiy_ws* ws, BellCall c, double* v_a, double* v_b, dou
         // entries stay the caller's; every ring slot starts as a copy of them to match
         // (feasibility depends on (r, w, grids) only, so it is fixed within a solve).
         for (int q = 0; q < Rp; ++q) {
-            AIY_HIP(hipMemcpyAsync(ws->spec_idx + (size_t)q * n, uidx, n * sizeof(int),
+            AIY_HIP(hipMemcpyAsync(sp.idx + (size_t)q * n, uidx, n * sizeof(int),
                                    hipMemcpyDeviceToDevice, st));
             double* const src[3] = {upk, upc, upl};
             for (int p = 0; p < 3; ++p)
                 if (src[p])
-                    AIY_HIP(hipMemcpyAsync(ws->spec_pol + ((size_t)q * 3 + p) * n, src[p], vb,
+                    AIY_HIP(hipMemcpyAsync(sp.pol + ((size_t)q * 3 + p) * n, src[p], vb,
                                            hipMemcpyDeviceToDevice, st));
         }
     }
@@ -660,10 +502,10 @@ static int bell_solve_spec(aiy_ws* ws, BellCall c, double* v_a, double* v_b, dou
             c.diff_out = (t == m - 1) ? reinterpret_cast<double*>(dslot(g)) : nullptr;
             AIY_TRY(bell_sweep_dev(ws, c, st));
         }
-        unsigned long long* h = ws->spec_hdiff + (size_t)hb_next * 2 * D;
-        AIY_HIP(hipMemcpyAsync(h, ws->spec_diff, 2 * (size_t)D * sizeof(unsigned long long),
+        unsigned long long* h = sp.hdiff + (size_t)hb_next * 2 * D;
+        AIY_HIP(hipMemcpyAsync(h, sp.diff, 2 * (size_t)D * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, st));
-        AIY_HIP(hipEventRecord(ws->spec_ev[hb_next], st));
+        AIY_HIP(hipEventRecord(sp.ev[hb_next], st));
         q[nq++] = Batch{enq, m, hb_next};
         hb_next ^= 1;
         enq += m;
@@ -673,8 +515,8 @@ static int bell_solve_spec(aiy_ws* ws, BellCall c, double* v_a, double* v_b, dou
     while (nq > 0) {
         if (nq < 2 && enq < max_iter) AIY_TRY(enqueue());
         const Batch b = q[0];
-        AIY_TRY(wait_event(ws->spec_ev[b.hb]));
-        const unsigned long long* hs = ws->spec_hdiff + (size_t)b.hb * 2 * D;
+        AIY_TRY(wait_event(sp.ev[b.hb]));
+        const unsigned long long* hs = sp.hdiff + (size_t)b.hb * 2 * D;
         for (int64_t t = 0; t < b.m; ++t) {
             const unsigned long long* h = hs + 2 * ((b.s0 + 1 + t) % D);
             double d = NAN;  // {max|Δ| bits, any non-NaN} (reduce_slots_kernel)
@@ -719,7 +561,7 @@ int bell_solve_dev(aiy_ws* ws, BellCall c, double* v_a, double* v_b, double tol,
         if (bytes <= ((size_t)8 << 30)) {
             int rc = bell_solve_spec(ws, c, v_a, v_b, tol, max_iter, iters, out_new, st);
             if (rc != AIY_NO_MEMORY) return rc;
-            ws->free_spec();  // no room for the rings: one synchronisation per sweep instead
+            ws->spec = SpecRings{};  // no room for the rings: one synchronisation per sweep instead
         }
     }
     double* cur = v_a;
@@ -785,41 +627,43 @@ int bell_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w
     }
     if ((size_t)C * n > (size_t)INT32_MAX) return fail(AIY_BAD_SHAPE, "C*N*Na must fit int32");
     const int nb8 = (int)((ws->Na + 7) / 8), nb512 = (int)((ws->Na + 511) / 512);
-    if (ws->bC != C) {
-        ws->free_batch();
-        AIY_TRY(dalloc(&ws->bEV, C * n));
-        AIY_TRY(dalloc(&ws->bDt, C * n));
-        AIY_TRY(dalloc(&ws->bDm8, (size_t)C * ws->N * nb8));
-        AIY_TRY(dalloc(&ws->bDm512, (size_t)C * ws->N * nb512));
-        AIY_TRY(dalloc(&ws->bbest0, C * n));
-        AIY_TRY(dalloc(&ws->bidx0, C * n));
-        AIY_TRY(dalloc(&ws->bmom, C * n));
-        AIY_HIP(hipMemset(ws->bmom, 0, C * n * sizeof(int)));
-        AIY_TRY(dalloc(&ws->bkf, C * n));
-        AIY_TRY(dalloc(&ws->bstop, (size_t)C));
-        AIY_TRY(dalloc(&ws->bslots, (size_t)C * 2 * 2 * kDiffSlots));
-        AIY_TRY(dalloc(&ws->brw, 2 * (size_t)C));
-        AIY_HIP(hipHostMalloc((void**)&ws->hstop, C * sizeof(int)));
-        AIY_HIP(hipHostMalloc((void**)&ws->hslots, (size_t)C * 2 * kDiffSlots * sizeof(unsigned long long)));
-        ws->bC = C;
+    BatchBlocks& bb = ws->batch;
+    if (bb.C != C) {
+        bb = BatchBlocks{};
+        AIY_TRY(bb.EV.ensure(C * n));
+        AIY_TRY(bb.Dt.ensure(C * n));
+        AIY_TRY(bb.Dm8.ensure((size_t)C * ws->N * nb8));
+        AIY_TRY(bb.Dm512.ensure((size_t)C * ws->N * nb512));
+        AIY_TRY(bb.best0.ensure(C * n));
+        AIY_TRY(bb.idx0.ensure(C * n));
+        AIY_TRY(bb.mom.ensure(C * n));
+        AIY_HIP(hipMemset(bb.mom, 0, C * n * sizeof(int)));
+        AIY_TRY(bb.kf.ensure(C * n));
+        AIY_TRY(bb.stop.ensure((size_t)C));
+        AIY_TRY(bb.slots.ensure((size_t)C * 2 * 2 * kDiffSlots));
+        AIY_TRY(bb.rw.ensure(2 * (size_t)C));
+        AIY_TRY(bb.hstop.ensure((size_t)C));
+        AIY_TRY(bb.hslots.ensure((size_t)C * 2 * kDiffSlots));
+        bb.C = C;
     }
     AIY_TRY(ws_ensure_bell(ws, 1));  // diff/hitcount scratch and events (single-rate buffers)
-    AIY_HIP(hipMemcpyAsync(ws->brw, r, C * sizeof(double), hipMemcpyHostToDevice, st));
-    AIY_HIP(hipMemcpyAsync(ws->brw + C, w, C * sizeof(double), hipMemcpyHostToDevice, st));
-    AIY_HIP(hipMemsetAsync(ws->bstop, 0, C * sizeof(int), st));
+    AIY_HIP(hipMemcpyAsync(bb.rw, r, C * sizeof(double), hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemcpyAsync(bb.rw + C, w, C * sizeof(double), hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemsetAsync(bb.stop, 0, C * sizeof(int), st));
     BellArgs A{};
     A.N = (int)ws->N; A.Na = (int)ws->Na; A.Nl = 1; A.labor = false; A.np = np;
     A.coarse = ws->coarse; A.CK = ws->CK;
-    A.variant = ws->variant >= 0 ? ws->variant : (ws->Na <= 4096 ? 0 : 16 | 1 << 21);
-    A.variant &= ~(1 | 2 | 4 | 8);  // one state per lane, one wave per tile, tree screen
+    A.variant = ws->variant >= 0 ? ws->variant
+                                   : (ws->Na <= 4096 ? 0 : kVarXcdOrder | kVarDriftExtrap);
+    A.variant &= ~kVarGeometryMask;  // one state per lane, one wave per tile, tree screen
     A.ev_mfma = bell_ev_mfma(A.N, ws->variant);
     A.beta = beta; A.sigma = sigma; A.a = a; A.s = s; A.P = P;
-    A.EV = ws->bEV; A.Dt = ws->bDt; A.Dm8 = ws->bDm8; A.Dm512 = ws->bDm512;
+    A.EV = bb.EV; A.Dt = bb.Dt; A.Dm8 = bb.Dm8; A.Dm512 = bb.Dm512;
     A.nb = (int)((ws->Na + 63) / 64); A.nb8 = nb8; A.nb512 = nb512;
-    A.tree = true; A.best0 = ws->bbest0; A.idx0 = ws->bidx0; A.kf = ws->bkf; A.mom = ws->bmom;
+    A.tree = true; A.best0 = bb.best0; A.idx0 = bb.idx0; A.kf = bb.kf; A.mom = bb.mom;
     A.hitcount = ws->count_hits ? ws->hitcount : nullptr;
-    A.idx = idx; A.pk = pk; A.pc = pc; A.diff = ws->bslots;
-    A.C = (int)C; A.rv = ws->brw; A.wv = ws->brw + C; A.stop = ws->bstop;
+    A.idx = idx; A.pk = pk; A.pc = pc; A.diff = bb.slots;
+    A.C = (int)C; A.rv = bb.rw; A.wv = bb.rw + C; A.stop = bb.stop;
     AIY_TRY(launch_bell_kf(A, st));  // per-candidate feasible prefixes, once per solve
     ws->kf_ok = false;               // (the single-rate kf cache is not this table)
     double* buf[2] = {v_a, v_b};
@@ -834,36 +678,36 @@ int bell_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w
             A.parity = (int)(g & 1);
             A.hint = (g == 1 && !use_hint) ? nullptr : idx;
             if (A.ev_mfma) AIY_TRY(launch_bell_ev_mfma(A, st));
-            AIY_TRY(launch_bell_table_batch(A, ws->bslots, (int)g, tol, st));
+            AIY_TRY(launch_bell_table_batch(A, bb.slots, (int)g, tol, st));
             if (!A.hint) AIY_TRY(launch_bell_init(A, st));
             AIY_TRY(ws_timing_begin(ws, st));
             AIY_TRY(launch_bell_tree(A, st));
             AIY_TRY(ws_timing_end(ws, st));
         }
         --g;  // sweeps launched so far
-        AIY_HIP(hipMemcpyAsync(ws->hstop, ws->bstop, C * sizeof(int), hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipMemcpyAsync(bb.hstop, bb.stop, C * sizeof(int), hipMemcpyDeviceToHost, st));
         AIY_HIP(hipStreamSynchronize(st));
         all_stopped = true;
-        for (int64_t c = 0; c < C; ++c) all_stopped = all_stopped && ws->hstop[c] != 0;
+        for (int64_t c = 0; c < C; ++c) all_stopped = all_stopped && bb.hstop[c] != 0;
     }
     // candidates still running after the last sweep G = max_iter: fold their sweep-G slots
     // (its :85 test), else the loop was exhausted and v_old = v_new (:88)
     const int64_t G = g;
     bool any_running = false;
-    for (int64_t c = 0; c < C; ++c) any_running = any_running || ws->hstop[c] == 0;
+    for (int64_t c = 0; c < C; ++c) any_running = any_running || bb.hstop[c] == 0;
     if (any_running) {
         for (int64_t c = 0; c < C; ++c)
-            if (ws->hstop[c] == 0)
-                AIY_HIP(hipMemcpyAsync(ws->hslots + c * 2 * kDiffSlots,
-                                       ws->bslots + ((size_t)c * 2 + (G & 1)) * 2 * kDiffSlots,
+            if (bb.hstop[c] == 0)
+                AIY_HIP(hipMemcpyAsync(bb.hslots + c * 2 * kDiffSlots,
+                                       bb.slots + ((size_t)c * 2 + (G & 1)) * 2 * kDiffSlots,
                                        2 * kDiffSlots * sizeof(unsigned long long),
                                        hipMemcpyDeviceToHost, st));
         AIY_HIP(hipStreamSynchronize(st));
     }
     for (int64_t c = 0; c < C; ++c) {
-        int64_t it = ws->hstop[c];
+        int64_t it = bb.hstop[c];
         if (it == 0) {
-            const double d = fold_slots_host(ws->hslots + c * 2 * kDiffSlots);
+            const double d = fold_slots_host(bb.hslots + c * 2 * kDiffSlots);
             it = G;
             if (!(d < tol))  // exhausted: v_old = v_new after the last sweep
                 AIY_HIP(hipMemcpyAsync(buf[(G - 1) & 1] + c * n, buf[G & 1] + c * n,
@@ -904,26 +748,15 @@ int aiy_ws_create(int64_t N, int64_t Na, int64_t Nl, aiy_ws** out) {
     ws->Na = Na;
     ws->Nl = Nl < 1 ? 1 : Nl;
     (void)hipGetDevice(&ws->dev);
-    ws->ev_start.resize(64);
-    ws->ev_stop.resize(64);
-    for (int q = 0; q < 64; ++q) {
-        if (hipEventCreate(&ws->ev_start[q]) != hipSuccess ||
-            hipEventCreate(&ws->ev_stop[q]) != hipSuccess) {
-            aiy_ws_destroy(ws);
-            return fail(AIY_HIP_ERROR, "hipEventCreate failed");
-        }
+    if (ws->ev_start.create(64, 0) != AIY_OK || ws->ev_stop.create(64, 0) != AIY_OK) {
+        delete ws;
+        return AIY_HIP_ERROR;
     }
     *out = ws;
     return AIY_OK;
 }
 
 int aiy_ws_destroy(aiy_ws* ws) {
-    if (!ws) return AIY_OK;
-    ws->free_all();
-    for (auto& e : ws->ev_start)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : ws->ev_stop)
-        if (e) (void)hipEventDestroy(e);
     delete ws;
     return AIY_OK;
 }
@@ -938,7 +771,7 @@ int aiy_ws_set_timing(aiy_ws* ws, int enable) {
     ws->launches = 0;
     if (ws->hitcount) AIY_HIP(hipMemset(ws->hitcount, 0, 4 * kDiffSlots * sizeof(unsigned long long)));
     if (ws->tracing && ws->trace)  // records of an earlier geometry must not linger
-        AIY_HIP(hipMemset(ws->trace, 0, 16 * (size_t)ws->trace_cap * sizeof(long long)));
+        AIY_HIP(hipMemset(ws->trace, 0, ws->trace.cap() * sizeof(long long)));
     return AIY_OK;
 }
 
@@ -973,7 +806,7 @@ int aiy_ws_trace(aiy_ws* ws, int64_t* out, int64_t cap, int64_t* n) {
     if (!ws || !out || !n) return fail(AIY_BAD_ARG, "NULL argument");
     *n = 0;
     if (!ws->trace) return AIY_OK;
-    int64_t m = std::min(cap, ws->trace_cap);
+    int64_t m = std::min(cap, ws_trace_units(ws));
     AIY_HIP(hipMemcpy(out, ws->trace, 16 * (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost));
     *n = m;
     return AIY_OK;
@@ -1016,7 +849,7 @@ int aiy_ws_set_cu_exclusive(aiy_ws* ws, int on) {
 int aiy_ws_set_speculation(aiy_ws* ws, int max_batch) {
     if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
     if (max_batch < 0 || max_batch > 256) return fail(AIY_BAD_ARG, "max_batch in [0, 256]");
-    if (max_batch != ws->spec_max) ws->free_spec();
+    if (max_batch != ws->spec_max) ws->spec = SpecRings{};
     ws->spec_max = max_batch;
     return AIY_OK;
 }
@@ -1028,11 +861,7 @@ int aiy_ws_set_search(aiy_ws* ws, int coarse_stride, int k_chunk) {
     if (coarse_stride) ws->coarse = coarse_stride;
     if (k_chunk != ws->CK) {
         ws->CK = k_chunk;
-        if (ws->partial) {
-            (void)hipFree(ws->partial);
-            ws->partial = nullptr;
-            ws->partial_cap = 0;
-        }
+        ws->partial.release();  // refilled (-1) at the next sweep
     }
     return AIY_OK;
 }

@@ -1,0 +1,109 @@
+// Owners of what a workspace allocates: DevBuf<T> (device), PinnedBuf<T> (pinned host), Events.
+// Non-copyable, movable (the source is left empty), freed by the destructor.  Host code only.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include <utility>
+#include <vector>
+
+#include "../../include/aiyagari_hip.h"
+
+namespace aiy {
+
+int fail(int code, const char* fmt, ...);
+
+// a Buf's memory: the two HIP allocators (a test substitutes malloc); not a policy to extend
+struct DevMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, 0); }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+
+template <class T, class Mem>
+class Buf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;  // elements
+
+public:
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    Buf& operator=(Buf&& o) noexcept {
+        Buf t(std::move(o));  // (frees what this held when it goes)
+        std::swap(p_, t.p_);
+        std::swap(cap_, t.cap_);
+        return *this;
+    }
+    ~Buf() { release(); }
+    // Room for n elements: nothing when the capacity suffices, else the old memory is freed and
+    // max(n, 1) elements allocated, contents undefined; *fresh (nullable) tells which, so the
+    // caller can fill the new memory or drop what it cached about the old.  On failure
+    // AIY_NO_MEMORY, and the buffer is empty.
+    int ensure(size_t n, bool* fresh = nullptr) {
+        if (fresh) *fresh = false;
+        if (p_ && cap_ >= n) return AIY_OK;
+        release();
+        const size_t m = n ? n : 1;
+        void* q = nullptr;
+        const hipError_t e = m > SIZE_MAX / sizeof(T) ? hipErrorOutOfMemory
+                                                      : Mem::alloc(&q, m * sizeof(T));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // reported here, not by the next launch's check
+            return fail(AIY_NO_MEMORY, "allocating %zu x %zu bytes failed: %s", m, sizeof(T),
+                        hipGetErrorString(e));
+        }
+        p_ = static_cast<T*>(q);
+        cap_ = m;
+        if (fresh) *fresh = true;
+        return AIY_OK;
+    }
+    void release() {
+        if (p_) Mem::free(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t cap() const { return cap_; }
+};
+template <class T>
+using DevBuf = Buf<T, DevMem>;
+template <class T>
+using PinnedBuf = Buf<T, PinnedMem>;
+
+// events created together and destroyed with their owner
+class Events {
+    std::vector<hipEvent_t> ev_;
+
+public:
+    Events() = default;
+    Events(Events&& o) noexcept : ev_(std::exchange(o.ev_, {})) {}
+    Events& operator=(Events&& o) noexcept {
+        Events t(std::move(o));
+        ev_.swap(t.ev_);
+        return *this;
+    }
+    ~Events() { release(); }
+    int create(int n, unsigned flags) {  // AIY_HIP_ERROR on failure, leaving none
+        release();
+        ev_.resize(n, nullptr);
+        for (hipEvent_t& e : ev_)
+            if (hipEventCreateWithFlags(&e, flags) != hipSuccess) {
+                release();
+                return fail(AIY_HIP_ERROR, "hipEventCreate failed");
+            }
+        return AIY_OK;
+    }
+    void release() {
+        for (hipEvent_t e : ev_)
+            if (e) (void)hipEventDestroy(e);
+        ev_.clear();
+    }
+    hipEvent_t operator[](size_t q) const { return ev_[q]; }
+    size_t size() const { return ev_.size(); }
+};
+
+}  // namespace aiy

@@ -28,17 +28,13 @@ constexpr int kDistSpecMax = 32;  // pushes per batch (two batches in flight)
 
 static int ensure_dist(aiy_ws* ws) {
     const size_t n = (size_t)ws->N * ws->Na;
-    if (!ws->d_key) AIY_HIP(hipMalloc((void**)&ws->d_key, n * sizeof(int)));
-    if (!ws->d_off) AIY_HIP(hipMalloc((void**)&ws->d_off, (n + ws->N) * sizeof(int)));
-    if (!ws->d_wr) AIY_HIP(hipMalloc((void**)&ws->d_wr, n * sizeof(double)));
-    if (!ws->d_mass) AIY_HIP(hipMalloc((void**)&ws->d_mass, n * sizeof(double)));
-    if (!ws->d_part) AIY_HIP(hipMalloc((void**)&ws->d_part, 260 * sizeof(double)));
-    if (!ws->gi) AIY_HIP(hipMalloc((void**)&ws->gi, 16 * sizeof(int)));
-    if (!ws->diff)
-        AIY_HIP(hipMalloc((void**)&ws->diff, 2 * kDiffSlots * sizeof(unsigned long long)));
-    if (!ws->hdiff)
-        AIY_HIP(hipHostMalloc((void**)&ws->hdiff, (2 * kDiffSlots + 4) * sizeof(unsigned long long)));
-    return AIY_OK;
+    AIY_TRY(ws->d_key.ensure(n));
+    AIY_TRY(ws->d_off.ensure(n + ws->N));
+    AIY_TRY(ws->d_wr.ensure(n));
+    AIY_TRY(ws->d_mass.ensure(n));
+    AIY_TRY(ws->d_part.ensure(260));
+    AIY_TRY(ws->gi.ensure(16));
+    return ws_ensure_diff(ws);
 }
 
 // the policy's plan; *fallback = the policy is not monotone (ordered-scan gather).
@@ -52,17 +48,11 @@ static int dist_plan(aiy_ws* ws, const int* idx, const double* kp, const double*
     A->N = (int)ws->N; A->Na = (int)ws->Na; A->lottery = (idx == nullptr);
     A->idx = idx; A->kp = kp; A->a = a; A->P = P;
     A->key = ws->d_key; A->off = ws->d_off; A->wr = ws->d_wr; A->mass = ws->d_mass;
-    A->diff = ws->diff; A->flags = (unsigned*)ws->gi;
+    A->diff = ws->diff; A->flags = ws->gi;
     A->trace = nullptr;
     if (ws->tracing) {  // (instrumentation) one record per push wave: ceil(Na/64)·N <= cap
         const int64_t cap = (int64_t)ws->N * ((ws->Na + 15) / 16);
-        if (ws->trace_cap < cap) {
-            if (ws->trace) (void)hipFree(ws->trace);
-            ws->trace = nullptr;
-            ws->trace_cap = 0;
-            AIY_HIP(hipMalloc((void**)&ws->trace, 16 * (size_t)cap * sizeof(long long)));
-            ws->trace_cap = cap;
-        }
+        AIY_TRY(ws_ensure_trace(ws, cap));
         AIY_HIP(hipMemsetAsync(ws->trace, 0, 16 * (size_t)cap * sizeof(long long), st));
         A->trace = ws->trace;
     }
@@ -119,18 +109,10 @@ int dist_stationary_dev(aiy_ws* ws, const double* lam0, const int* idx, const do
     const size_t n = (size_t)ws->N * ws->Na, nb = n * sizeof(double);
     const int SW = 2 * kDiffSlots;
     const size_t SB = (size_t)R * SW * sizeof(unsigned long long);
-    if (ws->dist_n != n || ws->dist_m != M) {
-        ws->free_dist_spec();
-        AIY_HIP(hipMalloc((void**)&ws->dist_ring, (size_t)R * nb));
-        AIY_HIP(hipMalloc((void**)&ws->dist_slots, SB));
-        AIY_HIP(hipHostMalloc((void**)&ws->dist_hslots, 2 * SB));
-        for (int b = 0; b < 2; ++b)
-            AIY_HIP(hipEventCreateWithFlags(&ws->dist_ev[b], hipEventDisableTiming));
-        ws->dist_n = n;
-        ws->dist_m = M;
-    }
-    auto slot = [&](int64_t g) { return ws->dist_ring + (size_t)(g % R) * n; };
-    auto sset = [&](int64_t g) { return ws->dist_slots + (size_t)(g % R) * SW; };
+    SlotRings& dr = ws->dist;
+    AIY_TRY(dr.ensure(n, M, SW));
+    auto slot = [&](int64_t g) { return dr.ring + (size_t)(g % R) * n; };
+    auto sset = [&](int64_t g) { return dr.slots + (size_t)(g % R) * SW; };
     AIY_HIP(hipMemcpyAsync(slot(0), lam0, nb, hipMemcpyDeviceToDevice, st));
     AIY_HIP(hipMemsetAsync(sset(1), 0, SW * sizeof(unsigned long long), st));
     struct Batch {
@@ -165,9 +147,9 @@ int dist_stationary_dev(aiy_ws* ws, const double* lam0, const int* idx, const do
             ws_dispatch_commit(ws);
             AIY_TRY(rc);
         }
-        unsigned long long* h = ws->dist_hslots + (size_t)hb_next * R * SW;
-        AIY_HIP(hipMemcpyAsync(h, ws->dist_slots, SB, hipMemcpyDeviceToHost, st));
-        AIY_HIP(hipEventRecord(ws->dist_ev[hb_next], st));
+        unsigned long long* h = dr.hslots + (size_t)hb_next * R * SW;
+        AIY_HIP(hipMemcpyAsync(h, dr.slots, SB, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipEventRecord(dr.ev[hb_next], st));
         q[nq++] = Batch{enq, m, hb_next};
         hb_next ^= 1;
         enq += m;
@@ -177,8 +159,8 @@ int dist_stationary_dev(aiy_ws* ws, const double* lam0, const int* idx, const do
     while (nq > 0) {
         if (nq < 2 && enq < max_iter) AIY_TRY(enqueue());  // keep the device busy while reading
         const Batch b = q[0];
-        AIY_TRY(wait_event(ws->dist_ev[b.hb]));
-        const unsigned long long* hs = ws->dist_hslots + (size_t)b.hb * R * SW;
+        AIY_TRY(wait_event(dr.ev[b.hb]));
+        const unsigned long long* hs = dr.hslots + (size_t)b.hb * R * SW;
         for (int64_t t = 0; t < b.m; ++t) {
             const double d = fold_slots_host(hs + (size_t)((b.s0 + 1 + t) % R) * SW);
             d_prev = d_last;

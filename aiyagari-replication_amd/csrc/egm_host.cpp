@@ -29,29 +29,18 @@ static bool egm_nonmonotone(const unsigned long long* slots, unsigned flag_word)
 }
 
 static int ensure_egm(aiy_ws* ws) {
-    size_t n = (size_t)ws->N * ws->Na;
-    if (!ws->g0) AIY_HIP(hipMalloc((void**)&ws->g0, n * sizeof(double)));
-    if (!ws->g1) AIY_HIP(hipMalloc((void**)&ws->g1, n * sizeof(double)));
-    if (!ws->gi) AIY_HIP(hipMalloc((void**)&ws->gi, 16 * sizeof(int)));
-    if (!ws->diff)
-        AIY_HIP(hipMalloc((void**)&ws->diff, 2 * kDiffSlots * sizeof(unsigned long long)));
-    if (!ws->hdiff)
-        AIY_HIP(hipHostMalloc((void**)&ws->hdiff, (2 * kDiffSlots + 4) * sizeof(unsigned long long)));
+    const size_t n = (size_t)ws->N * ws->Na;
+    bool fresh;
+    AIY_TRY(ws->g0.ensure(n));
+    AIY_TRY(ws->g1.ensure(n));
+    AIY_TRY(ws->gi.ensure(16));
+    AIY_TRY(ws_ensure_diff(ws));
     if (ws->tracing) {  // (instrumentation) one record per interp / chain wave: N·ntile
-        const int64_t cap = (int64_t)ws->N * ((ws->Na + 15) / 16);
-        if (ws->trace_cap < cap) {
-            if (ws->trace) (void)hipFree(ws->trace);
-            ws->trace = nullptr;
-            ws->trace_cap = 0;
-            AIY_HIP(hipMalloc((void**)&ws->trace, 16 * (size_t)cap * sizeof(long long)));
-            AIY_HIP(hipMemset(ws->trace, 0, 16 * (size_t)cap * sizeof(long long)));
-            ws->trace_cap = cap;
-        }
+        AIY_TRY(ws_ensure_trace(ws, (int64_t)ws->N * ((ws->Na + 15) / 16), &fresh));
+        if (fresh) AIY_HIP(hipMemset(ws->trace, 0, ws->trace.cap() * sizeof(long long)));
     }
-    if (!ws->egm_seg) {
-        AIY_HIP(hipMalloc((void**)&ws->egm_seg, n * sizeof(int)));
-        AIY_HIP(hipMemset(ws->egm_seg, 0xff, n * sizeof(int)));  // -1: no hint yet
-    }
+    AIY_TRY(ws->egm_seg.ensure(n, &fresh));
+    if (fresh) AIY_HIP(hipMemset(ws->egm_seg, 0xff, n * sizeof(int)));  // -1: no hint yet
     return AIY_OK;
 }
 
@@ -69,7 +58,7 @@ static EgmArgs egm_args(aiy_ws* ws, const double* c, const double* a, const doub
     A.c = c; A.a = a; A.s = s; A.P = P;
     A.ahat = ws->g0; A.cnext = ws->g1; A.cout = cout; A.pk = pk; A.pl = pl;
     A.diff = ws->diff;
-    A.flags = (unsigned*)ws->gi;
+    A.flags = ws->gi;
     A.trace = ws->tracing ? ws->trace : nullptr;  // (instrumentation; see ensure_egm)
     // interp1 segment hints (verified in the kernel; kEgmNoHints turns them off, A/B only)
     A.seg = egm_knob(ws, kEgmNoHints) ? nullptr : ws->egm_seg;
@@ -125,25 +114,17 @@ static int egm_solve_spec(aiy_ws* ws, const EgmArgs& A0, double* c0, double tol,
     const size_t n = (size_t)ws->N * ws->Na, nb = n * sizeof(double);
     const int SW = kEgmSlotWords;  // per step: {max bits, any} slots, then the flag word
     const size_t SB = (size_t)R * SW * sizeof(unsigned long long);
-    if (ws->egm_spec_n != n || ws->egm_spec_m != M) {
-        ws->free_egm_spec();
-        AIY_HIP(hipMalloc((void**)&ws->egm_ring, (size_t)R * nb));
-        AIY_HIP(hipMalloc((void**)&ws->egm_slots, SB));
-        AIY_HIP(hipHostMalloc((void**)&ws->egm_hslots, 2 * SB));
-        for (int b = 0; b < 2; ++b)
-            AIY_HIP(hipEventCreateWithFlags(&ws->egm_ev[b], hipEventDisableTiming));
-        ws->egm_spec_n = n;
-        ws->egm_spec_m = M;
-    }
-    auto slot = [&](int64_t g) { return ws->egm_ring + (size_t)(g % R) * n; };
-    auto sset = [&](int64_t g) { return ws->egm_slots + (size_t)(g % R) * SW; };
+    SlotRings& eg = ws->egm;
+    AIY_TRY(eg.ensure(n, M, SW));
+    auto slot = [&](int64_t g) { return eg.ring + (size_t)(g % R) * n; };
+    auto sset = [&](int64_t g) { return eg.slots + (size_t)(g % R) * SW; };
     AIY_HIP(hipMemcpyAsync(slot(0), c0, nb, hipMemcpyDeviceToDevice, st));
     // chained steps (the default for Na > 1,024): the RHS of step 1 here, then one launch per
     // step — interp1 of step g on â/c̃ pair (g−1) & 1, the RHS of step g+1 into pair g & 1
     const bool chain = !(A0.fused && A0.Na <= kEgmFusedMaxNa) && !egm_knob(ws, kEgmNoChain);
     if (chain) {
-        if (!ws->egm_x2) AIY_HIP(hipMalloc((void**)&ws->egm_x2, nb));
-        if (!ws->egm_y2) AIY_HIP(hipMalloc((void**)&ws->egm_y2, nb));
+        AIY_TRY(ws->egm_x2.ensure(n));
+        AIY_TRY(ws->egm_y2.ensure(n));
     }
     double* xs[2] = {ws->g0, ws->egm_x2};
     double* ys[2] = {ws->g1, ws->egm_y2};
@@ -194,9 +175,9 @@ static int egm_solve_spec(aiy_ws* ws, const EgmArgs& A0, double* c0, double tol,
         }
         m = std::min<int64_t>(std::max<int64_t>(m, 1), max_iter - enq);
         for (int64_t t = 0; t < m; ++t) AIY_TRY(step(enq + 1 + t));
-        unsigned long long* h = ws->egm_hslots + (size_t)hb_next * R * SW;
-        AIY_HIP(hipMemcpyAsync(h, ws->egm_slots, SB, hipMemcpyDeviceToHost, st));
-        AIY_HIP(hipEventRecord(ws->egm_ev[hb_next], st));
+        unsigned long long* h = eg.hslots + (size_t)hb_next * R * SW;
+        AIY_HIP(hipMemcpyAsync(h, eg.slots, SB, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipEventRecord(eg.ev[hb_next], st));
         q[nq++] = Batch{enq, m, hb_next};
         hb_next ^= 1;
         enq += m;
@@ -206,8 +187,8 @@ static int egm_solve_spec(aiy_ws* ws, const EgmArgs& A0, double* c0, double tol,
     while (nq > 0) {
         if (nq < 2 && enq < max_iter) AIY_TRY(enqueue());  // keep the device busy while reading
         const Batch b = q[0];
-        AIY_TRY(wait_event(ws->egm_ev[b.hb]));
-        const unsigned long long* hs = ws->egm_hslots + (size_t)b.hb * R * SW;
+        AIY_TRY(wait_event(eg.ev[b.hb]));
+        const unsigned long long* hs = eg.hslots + (size_t)b.hb * R * SW;
         for (int64_t t = 0; t < b.m; ++t) {
             const unsigned long long* h = hs + (size_t)((b.s0 + 1 + t) % R) * SW;
             if (egm_nonmonotone(h, (unsigned)h[2 * kDiffSlots])) {
@@ -365,11 +346,8 @@ int aiy_egm_solve_dev(aiy_ws* ws, double* policy_c, const double* a_grid, const 
             AIY_TRY(egm_solve_spec(ws, A, policy_c, tol, max_iter, &cur, &d, &it, st));
             AIY_HIP(hipMemcpyAsync(policy_c, cur, nb, hipMemcpyDeviceToDevice, st));
         } else {
+            AIY_TRY(ws->g2.ensure((size_t)ws->N * ws->Na));
             double* nxt = ws->g2;
-            if (!nxt) {
-                AIY_HIP(hipMalloc((void**)&ws->g2, nb));
-                nxt = ws->g2;
-            }
             while (d > tol && it < max_iter) {  // :74 (one read per step)
                 ++it;
                 AIY_TRY(egm_step_dev(ws, policy_c, a_grid, s, P, r, w, beta, sigma, amin,

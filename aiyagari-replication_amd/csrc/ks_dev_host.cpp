@@ -23,30 +23,30 @@ struct ks_dev {
     int nk = 0, nK = 0, K0 = 0, K1 = 0;
     int s0 = 0, s1 = 4;  // owned s blocks [s0, s1): all four, or one z's pair ((K, Z) slices)
     double beta = 0, k_min = 0, k_max = 0;
-    double* kg = nullptr;
-    double* kgt = nullptr;  // the grid's slope tables (launch_ks_grid_tables), 3·nk doubles
-    double* P = nullptr;
-    aiy::KsSlice* sl = nullptr;
-    double* dV = nullptr;
-    int* cols = nullptr;   // value columns (s*nK + K) this shard reads: own and K'_idx targets
+    aiy::DevBuf<double> kg;
+    aiy::DevBuf<double> kgt;  // the grid's slope tables (launch_ks_grid_tables), 3·nk doubles
+    aiy::DevBuf<double> P;
+    aiy::DevBuf<aiy::KsSlice> sl;
+    aiy::DevBuf<double> dV;
+    aiy::DevBuf<int> cols;  // value columns (s*nK + K) this shard reads: own and K'_idx targets
     int ncols = 0;
-    unsigned long long* slots = nullptr;
+    aiy::DevBuf<unsigned long long> slots;
     int* seg = nullptr;    // [node] segment hints: improve writes them, Howard checks and uses them
+    aiy::DevBuf<int> seg_mem;     // seg's memory, unless another handle's is used:
     ks_dev* seg_owner = nullptr;  // set: seg is that handle's array (ks_dev_share_hints)
     int sharers = 0;              // handles using this handle's seg array
-    int* own_cols = nullptr;      // the shard's own columns (direct schedule: its slopes)
+    aiy::DevBuf<int> own_cols;    // the shard's own columns (direct schedule: its slopes)
     int n_own = 0;
     // direct schedule (ks_dev_set_columns): device table of 4·nK value then 4·nK slope column
     // pointers into the owners' buffers; null = the caller's full arrays
     const double* const* colV = nullptr;
     // staged direct schedule (ks_dev_set_split): own columns whose four forecast columns are all
     // owned (interior) and the rest (boundary), device lists
-    int* cols_int = nullptr;
-    int* cols_bnd = nullptr;
+    aiy::DevBuf<int> cols_int, cols_bnd;
     int n_int = 0, n_bnd = 0;
     // staged sweeps: the copy blocks' arrival counter (device; [1]: the launch's go word) and
     // its running total (host)
-    unsigned long long* copy_cnt = nullptr;
+    aiy::DevBuf<unsigned long long> copy_cnt;
     unsigned long long copy_total = 0;
     unsigned long long launches = 0;  // staged launches so far (the go word's tokens)
 };
@@ -73,6 +73,10 @@ static KsArgs shard_args(const ks_dev* h) {
     A.coldV = h->colV ? h->colV + 4 * h->nK : nullptr;
     return A;
 }
+// a handle's allocation failures keep the code they always had (AIY_HIP_ERROR)
+static int ks_alloc(int rc) {
+    return rc == AIY_NO_MEMORY ? fail(AIY_HIP_ERROR, "ks_dev: %s", aiy_last_error()) : rc;
+}
 }  // namespace aiy
 
 using namespace aiy;
@@ -85,10 +89,6 @@ int ks_dev_destroy(ks_dev* h) {
         return fail(AIY_BAD_ARG, "ks_dev_destroy: %d handle(s) still share this handle's hints; "
                     "destroy them first", h->sharers);
     if (h->seg_owner) h->seg_owner->sharers--;
-    void* ps[] = {h->kg, h->kgt, h->P, h->sl, h->dV, h->cols, h->own_cols, h->slots,
-                  h->seg_owner ? nullptr : h->seg, h->cols_int, h->cols_bnd, h->copy_cnt};
-    for (void* q : ps)
-        if (q) (void)hipFree(q);
     delete h;
     return AIY_OK;
 }
@@ -137,18 +137,24 @@ int ks_dev_create_slice(const double* k_grid, const double* K_grid, const double
     h->ncols = (int)cols.size();
     h->n_own = (int)own.size();
     const size_t n = (size_t)nk * nK * 4;
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMalloc((void**)&h->kg, nk * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->kgt, 3 * nk * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->P, sizeof Pr);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->sl, sl.size() * sizeof(KsSlice));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->dV, n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->cols, cols.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->own_cols, own.size() * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->slots, 2 * kDiffSlots * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->seg, n * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(h->seg, 0, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->copy_cnt, 2 * sizeof(unsigned long long));
+    const int rc = [&]() -> int {
+        AIY_TRY(h->kg.ensure(nk));
+        AIY_TRY(h->kgt.ensure(3 * nk));
+        AIY_TRY(h->P.ensure(16));
+        AIY_TRY(h->sl.ensure(sl.size()));
+        AIY_TRY(h->dV.ensure(n));
+        AIY_TRY(h->cols.ensure(cols.size()));
+        AIY_TRY(h->own_cols.ensure(own.size()));
+        AIY_TRY(h->slots.ensure(2 * kDiffSlots));
+        AIY_TRY(h->seg_mem.ensure(n));
+        return h->copy_cnt.ensure(2);
+    }();
+    if (rc != AIY_OK) {
+        ks_dev_destroy(h);
+        return ks_alloc(rc);
+    }
+    h->seg = h->seg_mem;
+    hipError_t e = hipMemset(h->seg, 0, n * sizeof(int));
     if (e == hipSuccess) e = hipMemset(h->copy_cnt, 0, 2 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemcpy(h->kg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch_ks_grid_tables(h->kg, (int)nk, h->kgt, nullptr) == AIY_OK
@@ -230,17 +236,14 @@ int ks_dev_set_split(ks_dev* h, const int32_t* interior, int32_t n_int, const in
             return fail(AIY_BAD_ARG, "ks_dev_set_split: column %d is not an own column (or repeats)", c);
         seen[c] = 1;
     }
-    for (int** q : {&h->cols_int, &h->cols_bnd})
-        if (*q) {
-            AIY_HIP(hipFree(*q));
-            *q = nullptr;
-        }
+    h->cols_int.release();
+    h->cols_bnd.release();
     if (n_int) {
-        AIY_HIP(hipMalloc((void**)&h->cols_int, n_int * sizeof(int)));
+        AIY_TRY(ks_alloc(h->cols_int.ensure(n_int)));
         AIY_HIP(hipMemcpy(h->cols_int, interior, n_int * sizeof(int), hipMemcpyHostToDevice));
     }
     if (n_bnd) {
-        AIY_HIP(hipMalloc((void**)&h->cols_bnd, n_bnd * sizeof(int)));
+        AIY_TRY(ks_alloc(h->cols_bnd.ensure(n_bnd)));
         AIY_HIP(hipMemcpy(h->cols_bnd, boundary, n_bnd * sizeof(int), hipMemcpyHostToDevice));
     }
     h->n_int = n_int;
@@ -354,7 +357,7 @@ int ks_dev_share_hints(ks_dev* h, ks_dev* owner) {
     if (h->sharers > 0) return fail(AIY_BAD_ARG, "other handles share h's hints");
     if (h->seg_owner == owner) return AIY_OK;
     if (h->seg_owner) h->seg_owner->sharers--;
-    else AIY_HIP(hipFree(h->seg));
+    else h->seg_mem.release();
     h->seg = owner->seg;
     h->seg_owner = owner;
     owner->sharers++;

@@ -93,14 +93,8 @@ int aiy_sim_capital_dev(aiy_ws* ws, const double* policy_rows, const double* a_g
                         const double* uniforms, double* k_supply, double* sim_k,
                         int32_t* sim_z, int32_t* status, void* stream) {
     if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
-    const size_t kb = sim_par_scratch_bytes(T, 1);
-    if (T >= 2 && ws->sim_par != 0 && ws->sim_kcap < kb) {  // the chain's scratch (per workspace)
-        if (ws->sim_kbuf) AIY_HIP(hipFree(ws->sim_kbuf));
-        ws->sim_kbuf = nullptr;
-        ws->sim_kcap = 0;
-        AIY_HIP(hipMalloc((void**)&ws->sim_kbuf, kb));
-        ws->sim_kcap = kb;
-    }
+    if (T >= 2 && ws->sim_par != 0)  // the chain's scratch (per workspace), a size in bytes
+        AIY_TRY(ws->sim_kbuf.ensure((sim_par_scratch_bytes(T, 1) + sizeof(double) - 1) / sizeof(double)));
     return sim_capital_dev(policy_rows, (size_t)ws->Na, 1, a_grid, P, ws->N, ws->Na, z1, k1, T,
                            uniforms, k_supply, sim_k, sim_z, status, (hipStream_t)stream,
                            ws->cu_exclusive, ws->sim_par != 0 ? ws->sim_kbuf : nullptr,

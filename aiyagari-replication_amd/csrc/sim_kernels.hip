@@ -9,7 +9,6 @@
 // a_grid and the policy rows are staged in LDS when they fit (Na·(N+1) <= 18432 doubles),
 // otherwise read through L1/L2.
 // Uniform draws come from the host (MATLAB's rand stream), so the chain is reproducible.
-#include <atomic>
 #include <algorithm>
 
 #include "aiy_common.hpp"
@@ -1025,28 +1024,20 @@ int launch_sim_chain_par(const SimArgs& A, hipStream_t st, bool spread) {
     const size_t bytes = sizeof(double) * (size_t)(2 + 2 * A.N) * SS;
     const int g = std::max(A.C, 1);
     const bool path = A.sim_k || A.sim_z;
-    // the dynamic-LDS limit is raised once per instantiation, to the most any call asks for
-#define AIY_LDS_ONCE(K_, SS_)                                                                      \
-    do {                                                                                           \
-        static std::atomic<bool> lds_set{false};                                                   \
-        if (!lds_set) {                                                                            \
-            AIY_HIP(hipFuncSetAttribute((const void*)K_, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)sizeof(double) * (2 + 2 * 7) * SS_));                 \
-            lds_set = true;                                                                        \
-        }                                                                                          \
-    } while (0)
+    // the dynamic-LDS limit: the most any call asks of the instantiation (raise_dynamic_lds)
 #define AIY_PAR(SS_, PA_)                                                                          \
     do {                                                                                           \
+        constexpr int most = (int)sizeof(double) * (2 + 2 * 7) * SS_;                              \
         if (spread) {                                                                              \
-            AIY_LDS_ONCE((sim_par_seg_kernel<SS_, false>), SS_);                                   \
-            AIY_LDS_ONCE((sim_par_seg_kernel<SS_, true>), SS_);                                    \
-            AIY_LDS_ONCE((sim_par_sum_kernel<SS_>), SS_);                                          \
+            AIY_TRY((raise_dynamic_lds<sim_par_seg_kernel<SS_, false>>(most)));                    \
+            AIY_TRY((raise_dynamic_lds<sim_par_seg_kernel<SS_, true>>(most)));                     \
+            AIY_TRY((raise_dynamic_lds<sim_par_sum_kernel<SS_>>(most)));                           \
             sim_par_z_kernel<PA_><<<g, 1024, 0, st>>>(A);                                          \
             sim_par_seg_kernel<SS_, false><<<g * kParWaves, kParSegThreads, bytes, st>>>(A);       \
             sim_par_seg_kernel<SS_, true><<<g * kParWaves, kParSegThreads, bytes, st>>>(A);        \
             sim_par_sum_kernel<SS_><<<g, 1024, bytes, st>>>(A);                                    \
         } else {                                                                                   \
-            AIY_LDS_ONCE((sim_chain_par_kernel<SS_, PA_>), SS_);                                   \
+            AIY_TRY((raise_dynamic_lds<sim_chain_par_kernel<SS_, PA_>>(most)));                    \
             sim_chain_par_kernel<SS_, PA_><<<g, 1024, bytes, st>>>(A);                             \
         }                                                                                          \
     } while (0)
@@ -1058,7 +1049,6 @@ int launch_sim_chain_par(const SimArgs& A, hipStream_t st, bool spread) {
         else AIY_PAR(1024, false);
     }
 #undef AIY_PAR
-#undef AIY_LDS_ONCE
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }
@@ -1073,17 +1063,12 @@ int launch_sim_chain_pipe(const SimArgs& A, hipStream_t st) {
     const size_t bytes = A.exclusive ? std::max(tables, (size_t)kSimExclusiveLds) : tables;
     const int g = std::max(A.C, 1);
     const bool path = A.sim_k || A.sim_z;
-    // the dynamic-LDS limit is raised once per instantiation, to the most any call asks for
+    // the dynamic-LDS limit: the most any call asks of the instantiation (raise_dynamic_lds)
 #define AIY_PIPE(SS_, PA_)                                                                         \
     do {                                                                                           \
-        static std::atomic<bool> lds_set{false};                                                   \
-        if (!lds_set) {                                                                            \
-            constexpr int most = std::max((int)sizeof(double) * (2 + 2 * (SS_ == 512 ? 8 : 7)) * SS_, \
-                                          kSimExclusiveLds);                                       \
-            AIY_HIP(hipFuncSetAttribute((const void*)sim_chain_pipe_kernel<SS_, PA_>,              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, most));        \
-            lds_set = true;                                                                        \
-        }                                                                                          \
+        constexpr int most = std::max((int)sizeof(double) * (2 + 2 * (SS_ == 512 ? 8 : 7)) * SS_, \
+                                      kSimExclusiveLds);                                           \
+        AIY_TRY((raise_dynamic_lds<sim_chain_pipe_kernel<SS_, PA_>>(most)));                       \
         sim_chain_pipe_kernel<SS_, PA_><<<g, 128, bytes, st>>>(A);                                 \
     } while (0)
     if (SS == 512) {
@@ -1116,14 +1101,10 @@ int launch_sim_capital(const SimArgs& A, hipStream_t st) {
         if (need_pad <= kSimChainLdsMax) {
             const size_t tables = sizeof(double) * (size_t)need_pad;
             const size_t bytes = A.exclusive ? std::max(tables, (size_t)kSimExclusiveLds) : tables;
-            static std::atomic<bool> lds_set[2] = {false, false};
-            if (!lds_set[path]) {  // once per instantiation, to the most any call asks for
-                const void* fn = path ? (const void*)sim_chain_kernel<true, true>
-                                      : (const void*)sim_chain_kernel<true, false>;
-                const int most = std::max((int)sizeof(double) * kSimChainLdsMax, kSimExclusiveLds);
-                AIY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-                lds_set[path] = true;
-            }
+            // the most any call asks of the instantiation (raise_dynamic_lds)
+            constexpr int most = std::max((int)sizeof(double) * kSimChainLdsMax, kSimExclusiveLds);
+            AIY_TRY((path ? raise_dynamic_lds<sim_chain_kernel<true, true>>(most)
+                          : raise_dynamic_lds<sim_chain_kernel<true, false>>(most)));
             if (path) sim_chain_kernel<true, true><<<g, 256, bytes, st>>>(A);
             else sim_chain_kernel<true, false><<<g, 256, bytes, st>>>(A);
         } else {

@@ -1,34 +1,84 @@
 // Workspace (aiy_ws): per-shape device scratch owned by the library, reused across calls.
+// Every allocation is a DevBuf / PinnedBuf / Events member (devbuf.hpp), sized where it is used.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
-#include "../../include/aiyagari_hip.h"
+#include "aiy_common.hpp"
 #include "bellman.hpp"
+#include "devbuf.hpp"
+
+namespace aiy {
+using u64 = unsigned long long;
+// speculative VFI solve (bell_solve_spec): ring of 2m + 1 value buffers, 2m policy sets and one
+// folded-diff pair per sweep of a batch, for n states and m = spec_max
+struct SpecRings {
+    size_t n = 0;  // states per buffer the rings were sized for (0 = not allocated)
+    int m = 0;     // spec_max the rings were sized for
+    DevBuf<double> v;
+    DevBuf<int> idx;
+    DevBuf<double> pol;    // [2m][3][n] (k, c, l)
+    DevBuf<u64> diff;      // device [2 * 2m]: a pair per sweep
+    PinnedBuf<u64> hdiff;  // two copies (batches in flight)
+    Events ev;             // [2] end of each in-flight batch's copy
+};
+// speculative EGM solve (ring of policy_c, slot sets of 2*kDiffSlots + 2 words: diff slots + the
+// flag word) and speculative histogram iteration (ring of λ, slot sets of 2*kDiffSlots words):
+// 2m + 1 buffers of n doubles, a slot set per step
+struct SlotRings {
+    size_t n = 0;
+    int m = 0;
+    DevBuf<double> ring;
+    DevBuf<u64> slots;      // device [2m + 1][slot set]
+    PinnedBuf<u64> hslots;  // two copies (batches in flight)
+    Events ev;              // [2] end of each in-flight batch's slot copy
+    // sized for (n_, m_) with W words per slot set; another (n, m) drops the old rings first
+    int ensure(size_t n_, int m_, size_t W) {
+        if (n == n_ && m == m_) return AIY_OK;
+        *this = SlotRings{};
+        const size_t R = 2 * (size_t)m_ + 1;
+        AIY_TRY(ring.ensure(R * n_));
+        AIY_TRY(slots.ensure(R * W));
+        AIY_TRY(hslots.ensure(2 * R * W));
+        AIY_TRY(ev.create(2, hipEventDisableTiming));
+        n = n_;
+        m = m_;
+        return AIY_OK;
+    }
+};
+// batched candidate rates (config 4, aiy_vfi_solve_batch_dev): per-candidate blocks of the
+// tree-screen scratch, sized for C candidates
+struct BatchBlocks {
+    int64_t C = 0;
+    DevBuf<double> EV, Dt, Dm8, Dm512, best0;
+    DevBuf<int> idx0, mom, kf;
+    DevBuf<int> stop;       // device [C]
+    DevBuf<u64> slots;      // device [C][2][2*kDiffSlots]
+    DevBuf<double> rw;      // device [2][C]: r then w
+    PinnedBuf<int> hstop;   // [C]
+    PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
+};
+}  // namespace aiy
 
 struct aiy_ws {
+    template <class T>
+    using Dev = aiy::DevBuf<T>;
+    using u64 = aiy::u64;
     int64_t N = 0, Na = 0, Nl = 1;
     int dev = 0;
     // search knobs (aiy_ws_set_search)
     int coarse = 512;
     int CK = 1024;
-    int variant = -1;  // -1: by size (see bell_sweep_dev); EGM knobs: bits 18-20 (egm_knob)
-    // VFI scratch
-    double* EV = nullptr;
-    double2* T = nullptr;
-    float* T32 = nullptr;
-    double* Dm = nullptr;
-    double* Dm8 = nullptr;
-    double* Dt = nullptr;
-    double* Dm512 = nullptr;
-    double* best0 = nullptr;
-    int* idx0 = nullptr;
-    int* mom = nullptr;  // [N][Na] last sweep's argmax shift (tree kernel start-up heuristic)
-    int* touched = nullptr;
-    double* dis = nullptr;
-    int* kf = nullptr;
-    size_t kf_cap = 0;
+    int variant = -1;  // -1: by size (see bell_args); EGM knobs: bits 18-20 (egm_knob)
+    // VFI scratch (ws_ensure_bell)
+    Dev<double> EV;
+    Dev<double2> T;
+    Dev<float> T32;
+    Dev<double> Dm, Dm8, Dt, Dm512, best0;
+    Dev<int> idx0;
+    Dev<int> mom;  // [N][Na] last sweep's argmax shift (tree kernel start-up heuristic)
+    Dev<int> touched;
+    Dev<double> dis;
+    Dev<int> kf;
     // key of the cached kf table (feasible prefixes depend on r, w, a, s, L only)
     bool kf_ok = false;
     double kf_r = 0, kf_w = 0;
@@ -37,11 +87,10 @@ struct aiy_ws {
     const void* kf_L = nullptr;
     int64_t kf_Nl = 0;
     bool kf_lab = false;
-    int* tree_perm = nullptr;  // tree dispatch order for the cached kf (ws_tree_perm)
-    int perm_cap = 0, perm_slots = 0;
+    Dev<int> tree_perm;  // tree dispatch order for the cached kf (ws_tree_perm)
+    int perm_slots = 0;
     long long perm_key = 0;
-    int* kf_last = nullptr;    // [Nl][N][ntile] kf of each tile's last state (ws_tree_perm)
-    int kf_last_cap = 0;
+    Dev<int> kf_last;    // [Nl][N][ntile] kf of each tile's last state (ws_tree_perm)
     // disutility per labour level, cached with the key below (aiy_ws_invalidate resets)
     bool dis_ok = false;
     const void* dis_L = nullptr;
@@ -52,170 +101,47 @@ struct aiy_ws {
     int wide_max = -1, wide_S = 0, wide_NW = 0, wide_SB = 0;
     bool cu_exclusive = false;  // aiy_ws_set_cu_exclusive
     // A9 chains (aiy_ws_set_sim): -1 by size, 0 the serial kernels, 1 / 2 the speculative-
-    // segment chain (one workgroup / spread over 16) whenever it applies; its scratch (bytes)
+    // segment chain (one workgroup / spread over 16) whenever it applies; its scratch
     int sim_par = -1;
-    double* sim_kbuf = nullptr;
-    size_t sim_kcap = 0;
-    unsigned long long* wdiff = nullptr;  // device [2][2*kDiffSlots]: the set not current is zero
-    int wcur = 0;                         // the set the last wide sweep wrote
-    unsigned* wcnt = nullptr;             // device [N·ntile] per-tile arrival counters (zero)
-    size_t wcnt_cap = 0;
-    unsigned long long* wpart = nullptr;  // device [N·ntile][S][64][2] partial bests
-    size_t wpart_cap = 0;
-    bool last_wide = false;               // the last VFI sweep on this workspace was wide
-    unsigned long long* vdiff = nullptr;  // the diff slots the last VFI sweep wrote
+    Dev<double> sim_kbuf;
+    Dev<u64> wdiff;          // device [2][2*kDiffSlots]: the set not current is zero
+    int wcur = 0;            // the set the last wide sweep wrote
+    Dev<unsigned> wcnt;      // device [N·ntile] per-tile arrival counters (zero)
+    Dev<u64> wpart;          // device [N·ntile][S][64][2] partial bests
+    bool last_wide = false;  // the last VFI sweep on this workspace was wide
+    u64* vdiff = nullptr;    // (not owned) the diff slots the last VFI sweep wrote
     bool perm_ok = false;
-    int* partial = nullptr;
-    size_t partial_cap = 0;
-    unsigned long long* diff = nullptr;      // device [2*kDiffSlots] {max bits, any}
-    unsigned long long* hitcount = nullptr;  // device [4 * kDiffSlots]
-    long long* trace = nullptr;              // device [8 * trace_cap] (instrumentation)
-    int64_t trace_cap = 0;
+    Dev<int> partial;
+    Dev<u64> diff;           // device [2*kDiffSlots] {max bits, any}   (ws_ensure_diff)
+    Dev<u64> hitcount;       // device [4 * kDiffSlots]
+    Dev<long long> trace;    // device [16 * units] (instrumentation; ws_ensure_trace)
     bool tracing = false;
-    unsigned long long* hdiff = nullptr;     // pinned host [2*kDiffSlots + 4]
+    aiy::PinnedBuf<u64> hdiff;  // pinned host [2*kDiffSlots + 4]
     // histogram scratch (A10)
-    int* d_key = nullptr;
-    int* d_off = nullptr;   // [N][Na+1] run offsets of the policy (the plan)
-    double* d_wr = nullptr;
-    double* d_mass = nullptr;
-    double* d_part = nullptr;
-    // speculative histogram iteration: ring of dist_m + 1 λ buffers, per-push diff slots
-    size_t dist_n = 0;
-    int dist_m = 0;
-    double* dist_ring = nullptr;
-    unsigned long long* dist_slots = nullptr;   // device [2 dist_m + 1][2*kDiffSlots]
-    unsigned long long* dist_hslots = nullptr;  // pinned host, two copies (batches in flight)
-    hipEvent_t dist_ev[2] = {nullptr, nullptr};
-    void free_dist_spec() {
-        if (dist_ring) (void)hipFree(dist_ring);
-        if (dist_slots) (void)hipFree(dist_slots);
-        if (dist_hslots) (void)hipHostFree(dist_hslots);
-        for (auto& e : dist_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        dist_ring = nullptr; dist_slots = nullptr; dist_hslots = nullptr;
-        dist_n = 0; dist_m = 0;
-    }
+    Dev<int> d_key;
+    Dev<int> d_off;  // [N][Na+1] run offsets of the policy (the plan)
+    Dev<double> d_wr, d_mass, d_part;
+    aiy::SlotRings dist;  // speculative histogram iteration
     // generic scratch used by the EGM / distribution / simulation kernels
-    double* g0 = nullptr;
-    double* g1 = nullptr;
-    double* g2 = nullptr;
-    int* gi = nullptr;
-    // speculative solve (aiy_ws_set_speculation): ring of spec_max + 1 value buffers, spec_max
-    // policy sets and one folded-diff slot per sweep of a batch
+    Dev<double> g0, g1, g2;
+    Dev<unsigned> gi;  // [16] flag words (EGM, histogram)
+    // speculative solves (aiy_ws_set_speculation): batches of up to spec_max steps
     int spec_max = 16;
-    size_t spec_n = 0;  // states per buffer the rings were sized for (0 = not allocated)
-    double* spec_v = nullptr;
-    int* spec_idx = nullptr;
-    double* spec_pol = nullptr;                 // [spec_max][3][N*Na] (k, c, l)
-    int spec_m = 0;                             // spec_max the rings were sized for
-    unsigned long long* spec_diff = nullptr;    // device [2 * 2*spec_max]: a pair per sweep
-    unsigned long long* spec_hdiff = nullptr;   // pinned host, two copies (batches in flight)
-    hipEvent_t spec_ev[2] = {nullptr, nullptr};
-    // speculative EGM solve: ring of spec_max + 1 policy_c buffers, per-step diff slots + flag
-    size_t egm_spec_n = 0;
-    int egm_spec_m = 0;
-    double* egm_ring = nullptr;
-    unsigned long long* egm_slots = nullptr;    // device [2 spec_max + 1][2*kDiffSlots + 2]
-    unsigned long long* egm_hslots = nullptr;   // pinned host, two copies (batches in flight)
-    hipEvent_t egm_ev[2] = {nullptr, nullptr};  // end of each in-flight batch's slot copy
+    aiy::SpecRings spec;
+    aiy::SlotRings egm;
     // chained EGM solve (Na > 1,024): the second â / c̃ pair (step parity)
-    double* egm_x2 = nullptr;
-    double* egm_y2 = nullptr;
-    int* egm_seg = nullptr;  // [N][Na] interp1 segments of the last step (hints), -1 = none
-    void free_egm_spec() {
-        if (egm_ring) (void)hipFree(egm_ring);
-        if (egm_slots) (void)hipFree(egm_slots);
-        if (egm_hslots) (void)hipHostFree(egm_hslots);
-        for (auto& e : egm_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        egm_ring = nullptr; egm_slots = nullptr; egm_hslots = nullptr;
-        egm_spec_n = 0; egm_spec_m = 0;
-    }
-    // batched candidate rates (config 4, aiy_vfi_solve_batch_dev): per-candidate blocks of the
-    // tree-screen scratch, sized for bC candidates
-    int64_t bC = 0;
-    double* bEV = nullptr;
-    double* bDt = nullptr;
-    double* bDm8 = nullptr;
-    double* bDm512 = nullptr;
-    double* bbest0 = nullptr;
-    int* bidx0 = nullptr;
-    int* bmom = nullptr;
-    int* bkf = nullptr;
-    int* bstop = nullptr;                  // device [bC]
-    unsigned long long* bslots = nullptr;  // device [bC][2][2*kDiffSlots]
-    double* brw = nullptr;                 // device [2][bC]: r then w
-    int* hstop = nullptr;                  // pinned [bC]
-    unsigned long long* hslots = nullptr;  // pinned [bC][2*kDiffSlots]
-    void free_batch() {
-        void* ps[] = {bEV, bDt, bDm8, bDm512, bbest0, bidx0, bmom, bkf, bstop, bslots, brw};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-        if (hstop) (void)hipHostFree(hstop);
-        if (hslots) (void)hipHostFree(hslots);
-        bEV = bDt = bDm8 = bDm512 = bbest0 = brw = nullptr;
-        bidx0 = bkf = bstop = bmom = nullptr;
-        bslots = nullptr;
-        hstop = nullptr;
-        hslots = nullptr;
-        bC = 0;
-    }
+    Dev<double> egm_x2, egm_y2;
+    Dev<int> egm_seg;  // [N][Na] interp1 segments of the last step (hints), -1 = none
+    aiy::BatchBlocks batch;
     // timing of the dominant kernel
     bool timing = false, count_hits = false;
-    std::vector<hipEvent_t> ev_start, ev_stop;
+    aiy::Events ev_start, ev_stop;
     int ev_used = 0;
     double tot_ms = 0;
     int64_t launches = 0;
-
-    void free_spec() {
-        void* ps[] = {spec_v, spec_idx, spec_pol, spec_diff};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-        if (spec_hdiff) (void)hipHostFree(spec_hdiff);
-        for (auto& e : spec_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        spec_v = nullptr; spec_idx = nullptr; spec_pol = nullptr; spec_diff = nullptr;
-        spec_hdiff = nullptr; spec_n = 0; spec_m = 0;
-    }
-    void free_all() {
-        void* ps[] = {EV, T, T32, Dm, Dm8, Dt, Dm512, touched, best0, idx0, mom, dis, kf, partial, diff, hitcount, trace, g0, g1, g2, gi,
-                      d_key, d_off, d_wr, d_mass, d_part, egm_x2, egm_y2, egm_seg, tree_perm,
-                      kf_last, wdiff, wcnt, wpart, sim_kbuf};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-        free_spec();
-        free_batch();
-        free_egm_spec();
-        free_dist_spec();
-        if (hdiff) (void)hipHostFree(hdiff);
-        EV = nullptr; T = nullptr; T32 = nullptr; Dm = nullptr; Dm8 = nullptr; Dt = nullptr; Dm512 = nullptr; touched = nullptr; best0 = nullptr; dis = nullptr; kf = nullptr; kf_cap = 0;
-        kf_ok = false;
-        idx0 = nullptr; mom = nullptr; partial = nullptr; diff = nullptr; hitcount = nullptr; trace = nullptr; trace_cap = 0; hdiff = nullptr;
-        g0 = g1 = g2 = nullptr; gi = nullptr;
-        egm_x2 = egm_y2 = nullptr;
-        egm_seg = nullptr;
-        tree_perm = nullptr; perm_cap = 0; perm_ok = false;
-        kf_last = nullptr; kf_last_cap = 0;
-        wdiff = nullptr; wcnt = nullptr; wcnt_cap = 0; wpart = nullptr; wpart_cap = 0; wcur = 0;
-        sim_kbuf = nullptr; sim_kcap = 0;
-        last_wide = false; vdiff = nullptr; dis_ok = false;
-        d_key = d_off = nullptr; d_wr = d_mass = d_part = nullptr;
-        partial_cap = 0;
-    }
 };
 
 namespace aiy {
-// EGM A/B knobs on the workspace's variant word, above the VFI geometry bits (0-17), so a VFI
-// variant never changes the EGM path on a shared workspace
-constexpr int kEgmTwoLaunch = 1 << 18;  // the two-launch step even for Na <= 1,024
-constexpr int kEgmNoChain = 1 << 19;    // solve loop: two launches per step, no chaining
-constexpr int kEgmNoHints = 1 << 20;    // interp1 without the previous step's segment windows
 inline bool egm_knob(const aiy_ws* ws, int bit) { return ws->variant >= 0 && (ws->variant & bit); }
 struct BellCall {
     bool labor = false;
@@ -239,6 +165,11 @@ struct BellCall {
     void* prev_diff_out = nullptr;  // [2] u64: the previous sweep's folded {max bits, any}
 };
 int ws_ensure_bell(aiy_ws* ws, size_t partial_slots);
+// diff (device slots) and hdiff (their pinned copy + 4 words): VFI, EGM and histogram paths
+int ws_ensure_diff(aiy_ws* ws);
+// the trace buffer: 16 words per unit; *fresh (nullable) = newly allocated (contents undefined)
+int ws_ensure_trace(aiy_ws* ws, int64_t units, bool* fresh = nullptr);
+inline int64_t ws_trace_units(const aiy_ws* ws) { return (int64_t)(ws->trace.cap() / 16); }
 int ws_timing_begin(aiy_ws* ws, hipStream_t st);
 int ws_timing_end(aiy_ws* ws, hipStream_t st);
 int ws_timing_drain(aiy_ws* ws);
