@@ -74,6 +74,35 @@ using DevBuf = Buf<T, DevMem>;
 template <class T>
 using PinnedBuf = Buf<T, PinnedMem>;
 
+// batched EGM solve (aiy_egm_solve_batch_dev): the per-candidate inputs and results on the
+// device and their pinned copies, sized for the largest C seen (DM / PM: the two memories)
+template <class DM, class PM>
+struct EgmBatchBlocksT {
+    Buf<double, DM> rw;        // device [2][C]: r then w
+    Buf<long long, DM> iters;  // device [C]
+    Buf<double, DM> dist;      // device [C]
+    Buf<int, DM> status;       // device [C]
+    Buf<double, PM> hrw;       // pinned [2][C]
+    Buf<long long, PM> hiters;
+    Buf<double, PM> hdist;
+    Buf<int, PM> hstatus;
+    // room for C candidates; on failure the status of the first allocation that failed (what
+    // was allocated before it stays owned and is reused or freed as usual)
+    int ensure(size_t C) {
+        if (C > SIZE_MAX / 2) return fail(AIY_NO_MEMORY, "%zu candidates", C);
+        int rc = rw.ensure(2 * C);
+        if (rc == AIY_OK) rc = iters.ensure(C);
+        if (rc == AIY_OK) rc = dist.ensure(C);
+        if (rc == AIY_OK) rc = status.ensure(C);
+        if (rc == AIY_OK) rc = hrw.ensure(2 * C);
+        if (rc == AIY_OK) rc = hiters.ensure(C);
+        if (rc == AIY_OK) rc = hdist.ensure(C);
+        if (rc == AIY_OK) rc = hstatus.ensure(C);
+        return rc;
+    }
+};
+using EgmBatchBlocks = EgmBatchBlocksT<DevMem, PinnedMem>;
+
 // events created together and destroyed with their owner
 class Events {
     std::vector<hipEvent_t> ev_;

@@ -1,5 +1,6 @@
-// A4/A5 entry points: device tier (aiy_egm_step_dev) and MATLAB host tier (aiy_egm_*,
-// aiy_labor_egm_*).  policy arrays are Na x N column-major == [N][Na]: no transposes.
+// A4/A5 entry points: device tier (aiy_egm_step_dev, aiy_egm_solve_dev and the batched
+// multi-rate aiy_egm_solve_batch_dev) and MATLAB host tier (aiy_egm_*, aiy_labor_egm_*).
+// policy arrays are Na x N column-major == [N][Na]: no transposes.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,7 +15,12 @@
 
 namespace aiy {
 
+// set by fail_nonmonotone: lets the batched solve's per-candidate fallback tell this failure
+// (a candidate's status) from every other (the call's)
+static thread_local bool t_nonmonotone = false;
+
 static int fail_nonmonotone() {
+    t_nonmonotone = true;
     return fail(AIY_BAD_ARG, "endogenous grid a_hat is not increasing: interp1 in the "
                              "reference would sort it or fail (Aiyagari_EGM.m:95)");
 }
@@ -361,6 +367,98 @@ int aiy_egm_solve_dev(aiy_ws* ws, double* policy_c, const double* a_grid, const 
     AIY_HIP(hipStreamSynchronize(st));
     *iters = it;
     *dist = d;
+    return AIY_OK;
+}
+
+int aiy_egm_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                            double* policy_c, const double* a_grid, const double* s,
+                            const double* P, double beta, double sigma, double amin, int labor,
+                            double phi, double theta, double tol, int64_t max_iter,
+                            double* policy_k, double* policy_l, int64_t* iters, double* dist,
+                            int32_t* status, void* stream) {
+    if (!ws || !r || !w || !policy_c || !a_grid || !s || !P || !policy_k || !iters || !dist ||
+        !status || (labor && !policy_l))
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || C > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "need 1 <= C < 2^31");
+    if (ws->N > 16) return fail(AIY_BAD_SHAPE, "EGM kernels support N <= 16 productivity states");
+    if (ws->Na < 2) return fail(AIY_BAD_SHAPE, "need Na >= 2");
+    if (labor && !(phi == phi && theta == theta)) return fail(AIY_NON_FINITE, "phi/theta");
+    if (max_iter < 0) return fail(AIY_BAD_ARG, "max_iter must be >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)ws->N * ws->Na;
+    if (!(max_iter > 0 && 1.0 > tol)) {  // Aiyagari_EGM.m:74 tests dist = 1 first: no step
+        for (int64_t c = 0; c < C; ++c) {
+            iters[c] = 0;
+            dist[c] = 1.0;
+            status[c] = 0;
+        }
+        AIY_HIP(hipStreamSynchronize(st));
+        return AIY_OK;
+    }
+    const int64_t min_c = ws->egm_batch_min < 0 ? egm_batch_min_c(ws->N, ws->Na) : ws->egm_batch_min;
+    if (min_c > 0 && C >= min_c && egm_batch_fits(ws->N, ws->Na, labor != 0)) {
+        EgmBatchBlocks& bb = ws->egm_batch;
+        AIY_TRY(bb.ensure((size_t)C));
+        std::memcpy(bb.hrw.get(), r, sizeof(double) * C);
+        std::memcpy(bb.hrw.get() + C, w, sizeof(double) * C);
+        AIY_HIP(hipMemcpyAsync(bb.rw, bb.hrw, sizeof(double) * 2 * C, hipMemcpyHostToDevice, st));
+        EgmBatchArgs A{};
+        A.N = (int)ws->N; A.Na = (int)ws->Na; A.C = (int)C;
+        A.labor = labor != 0;
+        A.ns = is_int_ge(sigma, 1.0) ? (int)sigma : 0;
+        A.beta = beta; A.sigma = sigma; A.amin = amin; A.phi = phi; A.theta = theta; A.tol = tol;
+        A.max_iter = max_iter;
+        A.r = bb.rw; A.w = bb.rw + C;
+        A.a = a_grid; A.s = s; A.P = P;
+        A.c = policy_c; A.pk = policy_k; A.pl = labor ? policy_l : nullptr;
+        A.iters = bb.iters; A.dist = bb.dist; A.status = bb.status;
+        AIY_TRY(ws_timing_begin(ws, st));
+        AIY_TRY(launch_egm_solve_batch(A, st));
+        AIY_TRY(ws_timing_end(ws, st));
+        ++ws->egm_batch_launches;
+        AIY_HIP(hipMemcpyAsync(bb.hiters, bb.iters, sizeof(long long) * C, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipMemcpyAsync(bb.hdist, bb.dist, sizeof(double) * C, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipMemcpyAsync(bb.hstatus, bb.status, sizeof(int) * C, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipStreamSynchronize(st));  // the call's one synchronisation
+        for (int64_t c = 0; c < C; ++c) {
+            iters[c] = (int64_t)bb.hiters[c];
+            dist[c] = bb.hdist[c];
+            status[c] = bb.hstatus[c];
+        }
+        return AIY_OK;
+    }
+    // shapes whose arrays do not fit one CU's LDS, and fewer candidates than the threshold: the
+    // existing solve, one candidate after another; its non-monotone error is that candidate's
+    // status, not the call's
+    for (int64_t c = 0; c < C; ++c) {
+        t_nonmonotone = false;
+        const int rc = aiy_egm_solve_dev(ws, policy_c + c * n, a_grid, s, P, r[c], w[c], beta, sigma,
+                                         amin, labor, phi, theta, tol, max_iter, policy_k + c * n,
+                                         labor ? policy_l + c * n : nullptr, iters + c, dist + c,
+                                         stream);
+        ++ws->egm_batch_fallbacks;
+        status[c] = 0;
+        if (rc != AIY_OK) {
+            if (!t_nonmonotone) return rc;
+            status[c] = 1;
+            iters[c] = 0;
+            dist[c] = NAN;
+        }
+    }
+    return AIY_OK;
+}
+
+int aiy_ws_set_egm_batch(aiy_ws* ws, int min_candidates) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (min_candidates < -1) return fail(AIY_BAD_ARG, "min_candidates must be >= -1");
+    ws->egm_batch_min = min_candidates;
+    return AIY_OK;
+}
+
+int aiy_ws_egm_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_solves) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (launches) *launches = ws->egm_batch_launches;
+    if (fallback_solves) *fallback_solves = ws->egm_batch_fallbacks;
     return AIY_OK;
 }
 

@@ -15,18 +15,9 @@
 #include "aiy_common.hpp"
 #include "dispatch.hpp"
 #include "egm.hpp"
+#include "egm_dev.hpp"
 
 namespace aiy {
-
-__device__ __forceinline__ double uprime_dev(double c, double sigma, int ns) {
-    return ns > 0 ? 1.0 / aiy_ipow(c, ns) : aiy_pow(c, -sigma);  // c.^(-sigma)
-}
-
-__device__ __forceinline__ double labor_dev(double c, double ws, double sigma, int ns,
-                                            double phi, double theta) {
-    double x = (ws * uprime_dev(c, sigma, ns)) / phi;  // u_prime_l_inv(w s .* u_prime_c(c))
-    return (1.0 / theta == 1.0) ? x : aiy_pow(x, 1.0 / theta);
-}
 
 // Kernel 1: one workgroup per 64 asset nodes, one wave per productivity state.  Phase 1: wave m
 // evaluates u'(c_m) for its 64 nodes into LDS (once per (m, a), as the script's vectorised

@@ -5,6 +5,9 @@
 // candidates are spread over n_devices GPUs of this process, each device solving its share as
 // one batched solve (aiy_vfi_solve_batch_dev) and one batched launch of the chains.  The bracket
 // logic stays with the caller (the MATLAB script or ge_batch.py), exactly as in the reference.
+// aiy_egm_ge_batch is the same for the EGM scripts (Aiyagari_EGM.m:177-242, labour :174-240):
+// the batched EGM solve (aiy_egm_solve_batch_dev) from a common policy_c with the caller's w per
+// candidate; the device split, the uniforms and the chains are shared with aiy_ge_batch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +30,102 @@ struct GeShare {
     int rc = AIY_OK;
     std::string err;
 };
+
+// Splits C candidates over up to n_devices GPUs of this process (contiguous shares, the first
+// C % nd one larger; share d on device (current + d) % visible) and runs body(share) on each,
+// one host thread per device when there are several.  Holds the host-tier lock; the first
+// failing share's status and message are the call's.
+template <class Body>
+int ge_run_shares(int64_t C, int64_t N, int64_t Na, int n_devices, Body body) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(AIY_NO_DEVICE, "no HIP device visible");
+    const int nd = (int)std::min<int64_t>(std::max(n_devices, 1), std::min<int64_t>(ndev, C));
+    std::lock_guard<std::mutex> lk(host_mutex());
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    std::vector<GeShare> sh(nd);
+    for (int d = 0; d < nd; ++d) {
+        sh[d].dev = (cur + d) % ndev;
+        sh[d].c0 = d * (C / nd) + std::min<int64_t>(d, C % nd);
+        sh[d].cn = C / nd + (d < C % nd ? 1 : 0);
+        (void)hipSetDevice(sh[d].dev);
+        int rc = get_ctx(N, Na, 1, &sh[d].ctx);
+        if (rc != AIY_OK) {
+            (void)hipSetDevice(cur);
+            return rc;
+        }
+    }
+    auto run = [&](GeShare& g) {
+        g.rc = body(g);
+        if (g.rc != AIY_OK) g.err = aiy_last_error();
+    };
+    if (nd == 1) {
+        run(sh[0]);
+    } else {  // one host thread per device: the shares run concurrently
+        std::vector<std::thread> th;
+        for (auto& g : sh) th.emplace_back(run, std::ref(g));
+        for (auto& t : th) t.join();
+    }
+    (void)hipSetDevice(cur);
+    for (auto& g : sh)
+        if (g.rc != AIY_OK) return fail(g.rc, "%s", g.err.c_str());
+    return AIY_OK;
+}
+
+// the share's uniforms (column c of the (T-1) x C matrix = candidate c's draws) to its device
+int ge_stage_uniforms(GeShare& sh, int64_t T, const double* uniforms, double** dU) {
+    HostCtx* c = sh.ctx;
+    AIY_TRY(c->buf("ge_U", sizeof(double) * std::max<int64_t>(T - 1, 1) * sh.cn, (void**)dU));
+    if (T > 1)
+        AIY_HIP(hipMemcpyAsync(*dU, uniforms + sh.c0 * (T - 1), sizeof(double) * (T - 1) * sh.cn,
+                               hipMemcpyHostToDevice, c->st));
+    return AIY_OK;
+}
+
+// The share's batched chains over pk [cn][N][Na]: one batched launch per run of candidates
+// with skip[q] == 0 (skip nullable: all of them in one), then K_s and the find() flags back
+// (synchronises).  k_supply[c0 + q] is written for the candidates that ran; find_empty[q] for all.
+int ge_chains(GeShare& sh, const double* pk, const double* da, const double* dP, const double* dU,
+              int64_t N, int64_t Na, int64_t z1, double k1, int64_t T, const int32_t* skip,
+              double* k_supply, int* find_empty) {
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na;
+    double* dout;
+    int* dst;
+    AIY_TRY(c->buf("ge_out", sizeof(double) * C, (void**)&dout));
+    AIY_TRY(c->buf("ge_st", sizeof(int) * C, (void**)&dst));
+    SimArgs S{};
+    S.N = (int)N; S.Na = (int)Na; S.T = (int)T; S.z1 = (int)(z1 - 1); S.k1 = k1;
+    S.zs = (size_t)Na; S.as = 1; S.a = da; S.P = dP;
+    S.pcs = n; S.ucs = (size_t)std::max<int64_t>(T - 1, 0);
+    S.par = c->ws->sim_par;
+    if (S.par != 0)  // the speculative-segment chains' scratch (paths, state paths, flags)
+        AIY_TRY(c->buf("ge_kscr", sim_par_scratch_bytes(T, C), (void**)&S.kscr));
+    for (int64_t q = 0; q < C; ++q) find_empty[q] = 0;
+    for (int64_t q0 = 0; q0 < C;) {
+        if (skip && skip[q0]) {
+            ++q0;
+            continue;
+        }
+        int64_t q1 = q0;
+        while (q1 < C && !(skip && skip[q1])) ++q1;
+        S.pol = pk + q0 * n;
+        S.U = dU + q0 * S.ucs;
+        S.out = dout + q0;
+        S.status = dst + q0;
+        S.C = (int)(q1 - q0);
+        AIY_TRY(launch_sim_capital(S, c->st));
+        AIY_HIP(hipMemcpyAsync(k_supply + sh.c0 + q0, dout + q0, sizeof(double) * (q1 - q0),
+                               hipMemcpyDeviceToHost, c->st));
+        AIY_HIP(hipMemcpyAsync(find_empty + q0, dst + q0, sizeof(int) * (q1 - q0),
+                               hipMemcpyDeviceToHost, c->st));
+        q0 = q1;
+    }
+    AIY_HIP(hipStreamSynchronize(c->st));
+    return AIY_OK;
+}
 }  // namespace
 
 // one device's share: stage, batched solve, batched chains, outputs back
@@ -39,23 +138,18 @@ static int ge_share(GeShare& sh, const double* r, const double* v_rows, const do
     HostCtx* c = sh.ctx;
     const int64_t C = sh.cn;
     const size_t n = (size_t)N * Na, nb = n * sizeof(double);
-    double *da, *ds, *dP, *va, *vb, *pk, *dU, *dout;
-    int *idx, *dst;
+    double *da, *ds, *dP, *va, *vb, *pk, *dU;
+    int* idx;
     AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
     AIY_TRY(c->buf("ge_va", nb * C, (void**)&va));
     AIY_TRY(c->buf("ge_vb", nb * C, (void**)&vb));
     AIY_TRY(c->buf("ge_pk", nb * C, (void**)&pk));
     AIY_TRY(c->buf("ge_idx", sizeof(int) * n * C, (void**)&idx));
-    AIY_TRY(c->buf("ge_U", sizeof(double) * std::max<int64_t>(T - 1, 1) * C, (void**)&dU));
-    AIY_TRY(c->buf("ge_out", sizeof(double) * C, (void**)&dout));
-    AIY_TRY(c->buf("ge_st", sizeof(int) * C, (void**)&dst));
     // every candidate starts from the same v_old (the caller's warm start)
     AIY_HIP(hipMemcpyAsync(va, v_rows, nb, hipMemcpyHostToDevice, c->st));
     for (int64_t q = 1; q < C; ++q)
         AIY_HIP(hipMemcpyAsync(va + q * n, va, nb, hipMemcpyDeviceToDevice, c->st));
-    if (T > 1)
-        AIY_HIP(hipMemcpyAsync(dU, uniforms + sh.c0 * (T - 1), sizeof(double) * (T - 1) * C,
-                               hipMemcpyHostToDevice, c->st));
+    AIY_TRY(ge_stage_uniforms(sh, T, uniforms, &dU));
     std::vector<double> w(C);
     for (int64_t q = 0; q < C; ++q)  // Aiyagari_VFI.m:149 (w at the candidate r)
         w[q] = (1 - alpha) * std::pow(alpha / (r[sh.c0 + q] + delta), alpha / (1 - alpha));
@@ -63,22 +157,47 @@ static int ge_share(GeShare& sh, const double* r, const double* v_rows, const do
     AIY_TRY(bell_solve_batch_dev(c->ws, C, r + sh.c0, w.data(), va, vb, da, ds, dP, beta, sigma,
                                  tol, max_iter, 0, idx, pk, nullptr, iters + sh.c0, which.data(),
                                  c->st));
-    SimArgs S{};
-    S.N = (int)N; S.Na = (int)Na; S.T = (int)T; S.z1 = (int)(z1 - 1); S.k1 = k1;
-    S.pol = pk; S.zs = (size_t)Na; S.as = 1; S.a = da; S.P = dP; S.U = dU;
-    S.out = dout; S.status = dst;
-    S.C = (int)C; S.pcs = n; S.ucs = (size_t)std::max<int64_t>(T - 1, 0);
-    S.par = c->ws->sim_par;
-    if (S.par != 0)  // the speculative-segment chains' scratch (paths, state paths, flags)
-        AIY_TRY(c->buf("ge_kscr", sim_par_scratch_bytes(T, C), (void**)&S.kscr));
-    AIY_TRY(launch_sim_capital(S, c->st));
     std::vector<int> status(C);
-    AIY_HIP(hipMemcpyAsync(k_supply + sh.c0, dout, sizeof(double) * C, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(status.data(), dst, sizeof(int) * C, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
+    AIY_TRY(ge_chains(sh, pk, da, dP, dU, N, Na, z1, k1, T, nullptr, k_supply, status.data()));
     for (int64_t q = 0; q < C; ++q)
         if (status[q]) return fail(AIY_FIND_EMPTY, "candidate %lld: find(rand < cumsum(P(z,:))) empty",
                                    (long long)(sh.c0 + q + 1));
+    return AIY_OK;
+}
+
+// one device's share of aiy_egm_ge_batch: the batched EGM solve from the common policy_c, the
+// chains of the candidates that solved, statuses back
+static int egm_ge_share(GeShare& sh, const double* r, const double* w, const double* pc_start,
+                        const double* a, const double* s, const double* P, int64_t N, int64_t Na,
+                        double beta, double sigma, double amin, int labor, double phi,
+                        double theta, double tol, int64_t max_iter, int64_t z1, double k1,
+                        int64_t T, const double* uniforms, double* k_supply, int64_t* iters,
+                        int32_t* status) {
+    AIY_HIP(hipSetDevice(sh.dev));
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    double *da, *ds, *dP, *pc, *pk, *pl = nullptr, *dU;
+    AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
+    AIY_TRY(c->buf("ege_pc", nb * C, (void**)&pc));
+    AIY_TRY(c->buf("ge_pk", nb * C, (void**)&pk));
+    if (labor) AIY_TRY(c->buf("ege_pl", nb * C, (void**)&pl));
+    // every candidate starts from the same policy_c (Na x N column-major == [N][Na])
+    AIY_HIP(hipMemcpyAsync(pc, pc_start, nb, hipMemcpyHostToDevice, c->st));
+    for (int64_t q = 1; q < C; ++q)
+        AIY_HIP(hipMemcpyAsync(pc + q * n, pc, nb, hipMemcpyDeviceToDevice, c->st));
+    AIY_TRY(ge_stage_uniforms(sh, T, uniforms, &dU));
+    std::vector<double> dist(C);
+    int32_t* stq = status + sh.c0;
+    AIY_TRY(aiy_egm_solve_batch_dev(c->ws, C, r + sh.c0, w + sh.c0, pc, da, ds, dP, beta, sigma,
+                                    amin, labor, phi, theta, tol, max_iter, pk, pl,
+                                    iters + sh.c0, dist.data(), stq, c->st));
+    std::vector<int> empty(C, 0);
+    AIY_TRY(ge_chains(sh, pk, da, dP, dU, N, Na, z1, k1, T, stq, k_supply, empty.data()));
+    for (int64_t q = 0; q < C; ++q) {
+        if (!stq[q] && empty[q]) stq[q] = 2;  // find(rand < cumsum(P(z,:))) came up empty
+        if (stq[q]) k_supply[sh.c0 + q] = NAN;
+    }
     return AIY_OK;
 }
 
@@ -103,43 +222,44 @@ int aiy_ge_batch(const double* r, int64_t C, const double* v_start, const double
     for (int64_t q = 0; q < C; ++q)
         if (!std::isfinite(r[q]) || r[q] + delta <= 0)
             return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(AIY_NO_DEVICE, "no HIP device visible");
-    const int nd = (int)std::min<int64_t>(std::max(n_devices, 1), std::min<int64_t>(ndev, C));
     std::vector<double> rows((size_t)N * Na);
     cm_to_rows(v_start, N, Na, rows.data());
-    std::lock_guard<std::mutex> lk(host_mutex());
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    std::vector<GeShare> sh(nd);
-    for (int d = 0; d < nd; ++d) {  // contiguous shares, the first C % nd one larger
-        sh[d].dev = (cur + d) % ndev;
-        sh[d].c0 = d * (C / nd) + std::min<int64_t>(d, C % nd);
-        sh[d].cn = C / nd + (d < C % nd ? 1 : 0);
-        (void)hipSetDevice(sh[d].dev);
-        int rc = get_ctx(N, Na, 1, &sh[d].ctx);
-        if (rc != AIY_OK) {
-            (void)hipSetDevice(cur);
-            return rc;
-        }
-    }
-    auto run = [&](GeShare& g) {
-        g.rc = ge_share(g, r, rows.data(), a_grid, s, P, N, Na, alpha, delta, beta, sigma, tol,
+    AIY_TRY(ge_run_shares(C, N, Na, n_devices, [&](GeShare& g) {
+        return ge_share(g, r, rows.data(), a_grid, s, P, N, Na, alpha, delta, beta, sigma, tol,
                         max_iter, z1, k1, T, uniforms, k_supply, iters);
-        if (g.rc != AIY_OK) g.err = aiy_last_error();
-    };
-    if (nd == 1) {
-        run(sh[0]);
-    } else {  // one host thread per device: the shares run concurrently
-        std::vector<std::thread> th;
-        for (auto& g : sh) th.emplace_back(run, std::ref(g));
-        for (auto& t : th) t.join();
-    }
-    (void)hipSetDevice(cur);
-    for (auto& g : sh)
-        if (g.rc != AIY_OK) return fail(g.rc, "%s", g.err.c_str());
+    }));
     for (int64_t q = 0; q < C; ++q)  // Aiyagari_VFI.m:195
+        k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
+    return AIY_OK;
+}
+
+int aiy_egm_ge_batch(const double* r, const double* w, int64_t C, const double* policy_c_start,
+                     const double* a_grid, const double* s, const double* P, int64_t N,
+                     int64_t Na, double alpha, double delta, double beta, double sigma,
+                     double amin, int labor_flag, double phi, double theta, double labor,
+                     double tol, int64_t max_iter, int64_t z1, double k1, int64_t T,
+                     const double* uniforms, int n_devices, double* k_supply, double* k_demand,
+                     int64_t* iters, int32_t* status) {
+    if (!r || !w || !policy_c_start || !s || !P || !k_supply || !k_demand || !iters || !status ||
+        (T > 1 && !uniforms))
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need C >= 1, N >= 1, Na >= 2");
+    if (N > 16) return fail(AIY_BAD_SHAPE, "EGM kernels support N <= 16 productivity states");
+    if (T < 1 || T > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "T must be in [1, 2^31)");
+    if (z1 < 1 || z1 > N) return fail(AIY_BAD_ARG, "z1 (1-based) out of range");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    if (labor_flag && !(std::isfinite(phi) && std::isfinite(theta)))
+        return fail(AIY_NON_FINITE, "phi and theta must be finite");
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    for (int64_t q = 0; q < C; ++q)
+        if (!std::isfinite(r[q]) || r[q] + delta <= 0)
+            return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
+    AIY_TRY(ge_run_shares(C, N, Na, n_devices, [&](GeShare& g) {
+        return egm_ge_share(g, r, w, policy_c_start, a_grid, s, P, N, Na, beta, sigma, amin,
+                            labor_flag, phi, theta, tol, max_iter, z1, k1, T, uniforms, k_supply,
+                            iters, status);
+    }));
+    for (int64_t q = 0; q < C; ++q)  // K_d at the candidate r (Aiyagari_EGM.m:242)
         k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
     return AIY_OK;
 }

@@ -133,6 +133,12 @@ struct aiy_ws {
     Dev<double> egm_x2, egm_y2;
     Dev<int> egm_seg;  // [N][Na] interp1 segments of the last step (hints), -1 = none
     aiy::BatchBlocks batch;
+    // batched multi-rate EGM solve (aiy_egm_solve_batch_dev; aiy_ws_set_egm_batch): the one-launch
+    // path from egm_batch_min candidates on (-1: egm_batch_min_c, 0: never), its blocks, and how
+    // often each path ran on this workspace (aiy_ws_egm_batch_counts)
+    int egm_batch_min = -1;
+    aiy::EgmBatchBlocks egm_batch;
+    int64_t egm_batch_launches = 0, egm_batch_fallbacks = 0;
     // timing of the dominant kernel
     bool timing = false, count_hits = false;
     aiy::Events ev_start, ev_stop;

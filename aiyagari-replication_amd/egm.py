@@ -85,3 +85,23 @@ def egm_solve_dev(ws, policy_c, a_grid, s, P, r, w, beta, sigma, amin, tol, max_
                                   ptr(policy_l), C.byref(it), C.byref(dist),
                                   stream_handle(stream)))
     return it.value, dist.value
+
+
+def egm_solve_batch_dev(ws, r, w, policy_c, a_grid, s, P, beta, sigma, amin, tol, max_iter,
+                        policy_k, labor=False, phi=1.0, theta=1.0, policy_l=None, stream=None):
+    """aiy_egm_solve_batch_dev: C = len(r) candidate rates, each the whole solve loop at
+    (r[c], w[c]) from policy_c[c] (torch tensors [C][N][Na]; policy_c is updated in place).
+    Returns (iters, dist, status) as numpy arrays; status 1 marks a candidate whose endogenous
+    grid stopped increasing (the others are unaffected)."""
+    r = np.ascontiguousarray(r, np.float64)
+    w = np.ascontiguousarray(w, np.float64)
+    if r.ndim != 1 or w.shape != r.shape:
+        raise ValueError("r and w must be vectors of one length")
+    n = r.size
+    it = np.zeros(n, np.int64); dist = np.zeros(n); status = np.zeros(n, np.int32)
+    check(lib().aiy_egm_solve_batch_dev(ws.handle, i64(n), ptr(r), ptr(w), ptr(policy_c),
+                                        ptr(a_grid), ptr(s), ptr(P), d(beta), d(sigma), d(amin),
+                                        ip(1 if labor else 0), d(phi), d(theta), d(tol),
+                                        i64(max_iter), ptr(policy_k), ptr(policy_l), ptr(it),
+                                        ptr(dist), ptr(status), stream_handle(stream)))
+    return it, dist, status

@@ -60,13 +60,31 @@ class Trace:
     candidates: int = 0
 
 
+class NodeFailed(RuntimeError):
+    """The sequential loop's path visits a candidate whose evaluation failed (status != 0)."""
+
+    def __init__(self, node, status):
+        super().__init__(f"bisection step {node.depth} at r = {node.r!r}: candidate status "
+                         f"{status} (1: endogenous grid not increasing, 2: find() empty)")
+        self.node, self.status = node, status
+
+
+def _unpack(node, v):
+    """(K_s, K_d, iters) of a node's result; a result may carry a fourth field, its status
+    (the EGM evaluators): non-zero raises NodeFailed — only where the path reads the node."""
+    if len(v) > 3 and v[3] != 0:
+        raise NodeFailed(node, int(v[3]))
+    return v[0], v[1], v[2]
+
+
 def walk(nodes: list[Node], res: dict, lo: float, hi: float, steps: int, tr: Trace, tol: float):
     """Follow the sequential loop's path through an evaluated subtree (Aiyagari_VFI.m:195-204).
-    Returns (lo, hi, stopped)."""
+    Returns (lo, hi, stopped).  Raises NodeFailed when the path visits a node whose result
+    carries a non-zero status; failed nodes off the path are ignored."""
     by_key = {(n.lo, n.hi): n for n in nodes}
     for _ in range(steps):
         n = by_key[(lo, hi)]
-        Ks, Kd, it = res[(n.lo, n.hi)]
+        Ks, Kd, it = _unpack(n, res[(n.lo, n.hi)])
         tr.r_history.append(n.r); tr.k_supply.append(Ks); tr.k_demand.append(Kd)
         tr.iters.append(it)
         tr.r = n.r
@@ -114,7 +132,7 @@ def bisection(evaluate, r_low, r_high, max_steps=10, tol=1e-5) -> Trace:
     lo, hi = r_low, r_high
     for step in range(max_steps):
         n = Node(step + 1, (lo + hi) / 2, lo, hi)
-        Ks, Kd, it = evaluate(n)
+        Ks, Kd, it = _unpack(n, evaluate(n))
         tr.r_history.append(n.r); tr.k_supply.append(Ks); tr.k_demand.append(Kd)
         tr.iters.append(it)
         tr.r = n.r
@@ -129,12 +147,13 @@ def bisection(evaluate, r_low, r_high, max_steps=10, tol=1e-5) -> Trace:
     return tr
 
 
-def torch_allgather(mine, n_nodes):
+def torch_allgather(mine, n_nodes, fields=3):
     """The round's one collective (Aiyagari_VFI.m:193-204's decision inputs): every rank's
     (q, K_s, K_d, iters) rows as one float64 tensor [ceil(n_nodes / world), 4] (padding rows
     q = -1), gathered with all_gather_into_tensor — RCCL on GPU ranks (the tensor lives on the
     rank's current device), gloo on CPU.  All four fields are exact in float64 (q, iters are
-    small integers).  Returns the list over ranks of [(q, (K_s, K_d, iters)), ...]."""
+    small integers).  Returns the list over ranks of [(q, (K_s, K_d, iters)), ...].
+    fields=4 (the EGM evaluators): a fifth column carries each result's status."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size()
@@ -143,13 +162,14 @@ def torch_allgather(mine, n_nodes):
         raise ValueError(f"{len(mine)} results on one rank, at most {rows} expected")
     dev = (torch.device("cuda", torch.cuda.current_device())
            if dist.get_backend() == "nccl" else torch.device("cpu"))
-    buf = torch.full((rows, 4), -1.0, dtype=torch.float64)
-    for n, (q, (ks, kd, it)) in enumerate(mine):
-        buf[n] = torch.tensor([q, ks, kd, it], dtype=torch.float64)
-    out = torch.empty((world * rows, 4), dtype=torch.float64, device=dev)
+    buf = torch.full((rows, 1 + fields), -1.0, dtype=torch.float64)
+    for n, (q, v) in enumerate(mine):
+        buf[n] = torch.tensor([q, *v[:fields]], dtype=torch.float64)
+    out = torch.empty((world * rows, 1 + fields), dtype=torch.float64, device=dev)
     dist.all_gather_into_tensor(out, buf.to(dev))
-    got = out.cpu().view(world, rows, 4).tolist()
-    return [[(int(q), (ks, kd, int(it))) for q, ks, kd, it in part if q >= 0] for part in got]
+    got = out.cpu().view(world, rows, 1 + fields).tolist()
+    return [[(int(x[0]), (x[1], x[2], *(int(y) for y in x[3:]))) for x in part if x[0] >= 0]
+            for part in got]
 
 
 # ------------------------------------------------------------------------------ evaluators
@@ -258,3 +278,144 @@ def aiyagari_vfi_multisection(Na=400, levels=None, rank=0, world=1, allgather=No
     lo, hi = -0.05, 1 / cal["beta"] - 1
     return multisection(ev, lo, hi, levels=levels, rank=rank, world=world,
                         allgather=allgather if allgather else (torch_allgather if world > 1 else None))
+
+
+# ------------------------------------------------------------------- the EGM scripts (E2)
+def egm_calibration(Na=400, labor=False):
+    """The EGM scripts' calibration (labour: rho = .6, sigma_e = .2), the wage they freeze at
+    r0 = 0.04 (Aiyagari_EGM.m:61, labour :55) and the :64 starting policy_c [N][Na]."""
+    from . import calibration as cb
+    cal = cb.aiyagari(Na=Na, rho=0.6 if labor else 0.75, sigma_e=0.2 if labor else 0.75)
+    r0 = 0.04
+    w = cb.wage(r0, cal["alpha"], cal["delta"])
+    guess = np.tile((1 + r0) * cal["a_grid"] + w * np.mean(cal["s"]), (cal["N"], 1))
+    return cal, r0, w, guess
+
+
+def egm_evaluator(cal, solve, simulate, pc_start, w, labor=False, T=10000):
+    """Node evaluator for Aiyagari_EGM.m / Aiyagari_Endogenous_Labor_EGM.m: the EGM solve from
+    pc_start (the path-independent warm start) at the node's r and the scripts' stale w, MC
+    supply with the uniforms block of the node's depth, K_d.  Generic in the two callables (the
+    GPU path or the C oracle): solve(pc_start, r, w) -> dict(policy_k, iters[, status]);
+    simulate(policy_k, z1, k1, uniforms) -> K_s.  `labor` only documents which script the
+    callables restate.  Results are (K_s, K_d, iters, status); K_s is NaN where status != 0."""
+    from . import calibration as cb
+    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
+    head, blocks = mc_stream(T)
+    z1 = int(math.ceil(N * head[0]))
+    k1 = a[int(math.ceil(Na * head[1])) - 1]
+
+    def evaluate(node):
+        R = solve(pc_start, node.r, w)
+        st = int(R.get("status", 0))
+        Ks = math.nan if st else simulate(R["policy_k"], z1, k1, blocks[node.depth])
+        Kd = cb.capital_demand(node.r, cal["labor"], cal["alpha"], cal["delta"])
+        return (float(Ks), float(Kd), int(R["iters"]), st)
+    return evaluate
+
+
+def hip_egm_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, max_iter=1000, phi=1.0,
+                      theta=1.0):
+    """The evaluator on this rank's GPU, one solve after another (host tier); pc_start [N][Na]."""
+    from ._capi import AiyError
+    from .egm import egm_solve, labor_egm_solve
+    from .sim import sim_capital
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+
+    def solve(pc, r, w_):
+        try:
+            if labor:
+                return labor_egm_solve(pc.T, a, s, P, r, w_, cal["beta"], cal["sigma"], phi, theta,
+                                       cal["amin"], tol, max_iter)
+            return egm_solve(pc.T, a, s, P, r, w_, cal["beta"], cal["sigma"], cal["amin"], tol,
+                             max_iter)
+        except AiyError as e:
+            if "not increasing" not in str(e):
+                raise
+            return dict(policy_k=None, iters=0, status=1)
+
+    def simulate(pk, z1, k1, u):
+        return sim_capital(pk, a, P, z1, k1, u, vfi_layout=False)
+    return egm_evaluator(cal, solve, simulate, pc_start, w, labor, T)
+
+
+def egm_ge_batch_call(r, w, pc_start, cal, z1, k1, blocks, labor=False, phi=1.0, theta=1.0,
+                      tol=1e-5, max_iter=1000, n_devices=1):
+    """aiy_egm_ge_batch (C ABI): K_s, K_d, iteration count and status at every rate in `r`, each
+    from pc_start ([N][Na]) at wage w (a scalar or one per rate), with uniforms blocks[c]
+    (T-1 draws) for candidate c; z1 1-based."""
+    from ._capi import check, d, i64, ip, lib, ptr
+    r = np.ascontiguousarray(r, np.float64)
+    n = r.size
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
+    N, Na = cal["N"], cal["Na"]
+    U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
+    T = U.shape[0] + 1
+    pc = np.ascontiguousarray(pc_start, np.float64)  # [N][Na] == the script's Na x N
+    if pc.shape != (N, Na):
+        raise ValueError(f"pc_start must be [N][Na] = {(N, Na)}")
+    a = np.ascontiguousarray(cal["a_grid"], np.float64)
+    s = np.ascontiguousarray(cal["s"], np.float64)
+    P = np.asfortranarray(cal["P"], dtype=np.float64)
+    Ks, Kd = np.empty(n), np.empty(n)
+    it, st = np.empty(n, np.int64), np.empty(n, np.int32)
+    check(lib().aiy_egm_ge_batch(ptr(r), ptr(w), i64(n), ptr(pc), ptr(a), ptr(s), ptr(P), i64(N),
+                                 i64(Na), d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
+                                 d(cal["sigma"]), d(cal["amin"]), ip(1 if labor else 0), d(phi),
+                                 d(theta), d(cal["labor"]), d(tol), i64(max_iter), i64(z1),
+                                 d(k1), i64(T), ptr(U), ip(n_devices), ptr(Ks), ptr(Kd), ptr(it),
+                                 ptr(st)))
+    return Ks, Kd, it, st
+
+
+def hip_egm_batch_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, max_iter=1000,
+                            n_devices=1, phi=1.0, theta=1.0):
+    """The node evaluator on the batched device path: all of a round's nodes of this rank in
+    one aiy_egm_ge_batch call (one launch of the solves and one of the chains per GPU).  Same
+    per-node arithmetic as hip_egm_evaluator, so the traces are identical."""
+    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
+    head, blocks = mc_stream(T)
+    z1 = int(math.ceil(N * head[0]))
+    k1 = a[int(math.ceil(Na * head[1])) - 1]
+
+    def many(nodes):
+        Ks, Kd, it, st = egm_ge_batch_call([n.r for n in nodes], w, pc_start, cal, z1, k1,
+                                           [blocks[n.depth] for n in nodes], labor, phi, theta,
+                                           tol, max_iter, n_devices)
+        return [(float(Ks[q]), float(Kd[q]), int(it[q]), int(st[q])) for q in range(len(nodes))]
+
+    def evaluate(node):
+        return many([node])[0]
+    evaluate.many = many
+    return evaluate
+
+
+def aiyagari_egm_multisection(Na=400, labor=False, levels=None, rank=0, world=1, allgather=None,
+                              batched=True, T=10000, tol=1e-5, max_iter=1000, phi=1.0, theta=1.0):
+    """The GE of Aiyagari_EGM.m (labor: Aiyagari_Endogenous_Labor_EGM.m) with the candidate
+    rates of the next `levels` bisection steps evaluated at once.  Every rank solves r0 = 0.04
+    from the :64 guess, then the rounds, every candidate from that policy at the scripts' stale
+    w; batched=True runs a round's nodes of this rank in one aiy_egm_ge_batch call.  The scripts'
+    chained warm start takes the same bracket decisions (tests/test_egm_batch_gpu.py)."""
+    import functools
+    from .egm import egm_solve, labor_egm_solve
+    levels = auto_levels(world) if levels is None else levels
+    cal, r0, w, guess = egm_calibration(Na, labor)
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+    if labor:
+        R0 = labor_egm_solve(guess.T, a, s, P, r0, w, cal["beta"], cal["sigma"], phi, theta,
+                             cal["amin"], tol, max_iter)
+    else:
+        R0 = egm_solve(guess.T, a, s, P, r0, w, cal["beta"], cal["sigma"], cal["amin"], tol,
+                       max_iter)
+    pc0 = np.ascontiguousarray(R0["policy_c"].T)
+    if batched:
+        ev = hip_egm_batch_evaluator(cal, pc0, w, labor, T, tol, max_iter, 1, phi, theta)
+    else:
+        ev = hip_egm_evaluator(cal, pc0, w, labor, T, tol, max_iter, phi, theta)
+    if allgather is None and world > 1:
+        allgather = functools.partial(torch_allgather, fields=4)
+    tr = multisection(ev, -0.05, 1 / cal["beta"] - 1, levels=levels, rank=rank, world=world,
+                      allgather=allgather)
+    tr.iters = [int(R0["iters"])] + tr.iters
+    return tr

@@ -120,6 +120,17 @@ class Workspace:
         """Drop the cached feasibility table (after overwriting a_grid/s/L in place)."""
         check(lib().aiy_ws_invalidate(self._h))
 
+    def set_egm_batch(self, min_candidates: int = -1):
+        """The batched EGM solve's one-launch path from `min_candidates` on (-1: the measured
+        default, 1: whenever the shape fits, 0: never); results do not depend on it."""
+        check(lib().aiy_ws_set_egm_batch(self._h, ip(min_candidates)))
+
+    def egm_batch_counts(self):
+        """(one-launch batches, per-candidate fallback solves) of egm_solve_batch_dev so far."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib().aiy_ws_egm_batch_counts(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_variant(self, variant: int):
         """Screen-kernel geometry (tuning; results identical), see aiy_ws_set_variant."""
         check(lib().aiy_ws_set_variant(self._h, ip(variant)))

@@ -138,6 +138,23 @@ int aiy_ge_batch(const double* r, int64_t C, const double* v_start, const double
                  int64_t max_iter, int64_t z1, double k1, int64_t T, const double* uniforms,
                  int n_devices, double* k_supply, double* k_demand, int64_t* iters);
 
+/* E2 — the same for the EGM scripts: for each candidate c the body of one GE step of
+ * Aiyagari_EGM.m:177-242 (labor_flag: Aiyagari_Endogenous_Labor_EGM.m:174-240): the EGM solve
+ * at (r[c], w[c]) from policy_c_start (Na x N, the common warm start; the scripts keep w at its
+ * r0 value, so w is the caller's), the Monte-Carlo supply with column c of `uniforms`, and K_d
+ * from `labor` (the aggregate).  One batched solve (aiy_egm_solve_batch_dev) and one batched
+ * launch of the chains per device.  Out (C each): k_supply, k_demand, iters, status — 0 ok,
+ * 1 = a non-increasing endogenous grid ended the candidate's solve, 2 = find() came up empty in
+ * its chain; k_supply is NaN where status != 0 (the chain of a failed solve is skipped) and the
+ * call still returns AIY_OK.  a_grid strictly increasing; N <= 16. */
+int aiy_egm_ge_batch(const double* r, const double* w, int64_t C, const double* policy_c_start,
+                     const double* a_grid, const double* s, const double* P, int64_t N,
+                     int64_t Na, double alpha, double delta, double beta, double sigma,
+                     double amin, int labor_flag, double phi, double theta, double labor,
+                     double tol, int64_t max_iter, int64_t z1, double k1, int64_t T,
+                     const double* uniforms, int n_devices, double* k_supply, double* k_demand,
+                     int64_t* iters, int32_t* status);
+
 /* A6 — replaces Krusell_Smith_VFI.m:149-168 (policy improvement with fminbnd).
  * value, k_opt: k x K x S column-major (S = 4); B 4; P 4 x 4; params = 13 doubles {beta, alpha,
  * delta, k_min, k_max, ug, ub, l_bar, mu, z_grid(1), z_grid(2), eps_grid(1), eps_grid(2)}.  nfev (nullable,
@@ -375,6 +392,29 @@ int aiy_egm_solve_dev(aiy_ws* ws, double* policy_c, const double* a_grid, const 
                       double amin, int labor, double phi, double theta, double tol,
                       int64_t max_iter, double* policy_k, double* policy_l, int64_t* iters,
                       double* dist, void* stream);
+/* A4/A5 at C candidate rates on device: candidate c's whole solve loop at (r[c], w[c]) (host
+ * [C]) from policy_c[c] (device [C][N][Na], in: the start, out: the last policy_c_next);
+ * policy_k, policy_l (nullable unless labor): device [C][N][Na]; iters, dist, status: host [C].
+ * Where a candidate's arrays fit one CU's LDS (Na <= 1024 and (2N+1)·Na doubles, labour 3N·Na,
+ * within 160 KiB) and C is at least the workspace's threshold (aiy_ws_set_egm_batch), ONE launch
+ * runs one workgroup per candidate with no host read between steps and the call synchronises
+ * once; otherwise the candidates run one after another through aiy_egm_solve_dev.  For every
+ * candidate with status 0 the outputs equal one aiy_egm_solve_dev call bit for bit (max_iter = 0
+ * and tol >= 1 included).  status 1: a non-increasing endogenous grid ended that candidate's
+ * loop (its outputs are undefined); the others are unaffected and the call returns AIY_OK. */
+int aiy_egm_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                            double* policy_c, const double* a_grid, const double* s,
+                            const double* P, double beta, double sigma, double amin, int labor,
+                            double phi, double theta, double tol, int64_t max_iter,
+                            double* policy_k, double* policy_l, int64_t* iters, double* dist,
+                            int32_t* status, void* stream);
+/* the batched EGM solve's dispatch on this workspace: the one-launch path from min_candidates
+ * on (-1, the default: the measured threshold; 1: whenever the shape fits; 0:
+ * never).  Results do not depend on it. */
+int aiy_ws_set_egm_batch(aiy_ws* ws, int min_candidates);
+/* how often aiy_egm_solve_batch_dev took each path on this workspace since it was created:
+ * one-launch batches, and per-candidate solves of the other path (both nullable). */
+int aiy_ws_egm_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_solves);
 /* A9 on device: policy_rows [N][Na]; z1 0-based; k_supply (device double), sim_k/sim_z
  * nullable (device), status (device int32: 0 ok, 1 = find() empty). */
 int aiy_sim_capital_dev(aiy_ws* ws, const double* policy_rows, const double* a_grid,
