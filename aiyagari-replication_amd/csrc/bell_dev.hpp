@@ -118,6 +118,41 @@ __device__ __forceinline__ double screen_B(double best, int idx, double dis, int
     return nd * (best + dis) - kTau * nd * (fabs(best) + fabs(dis));
 }
 
+// min / max of x over the wave as a wave-uniform value (DPP ladder to lane 63, one v_readlane
+// pair); fmin / fmax drop NaN, so the result is NaN only when every lane's x is
+__device__ __forceinline__ double wave_fmin_d(double x) {
+    x = fmin(x, dpp_d<0xB1>(x));
+    x = fmin(x, dpp_d<0x4E>(x));
+    x = fmin(x, dpp_d<0x141>(x));
+    x = fmin(x, dpp_d<0x140>(x));
+    x = fmin(x, dpp_d<0x142, 0xa>(x));
+    x = fmin(x, dpp_d<0x143, 0xc>(x));
+    return readlane_d(x, 63);
+}
+__device__ __forceinline__ double wave_fmax_d(double x) {
+    x = fmax(x, dpp_d<0xB1>(x));
+    x = fmax(x, dpp_d<0x4E>(x));
+    x = fmax(x, dpp_d<0x141>(x));
+    x = fmax(x, dpp_d<0x140>(x));
+    x = fmax(x, dpp_d<0x142, 0xa>(x));
+    x = fmax(x, dpp_d<0x143, 0xc>(x));
+    return readlane_d(x, 63);
+}
+
+// Wave-level block bound: (dmax, a0) is one block's bound in this lane, bmin the minimum of the
+// wave's bars and cmax the maximum of its cash on hand (both wave-uniform).  True whenever some
+// sub-state of some lane passes the per-lane bound (dmax − B)·max(coh − a0, 0)^NP ≥ kThr: the
+// operation sequence is screen_t's, every step of it is monotone in floating point (dmax − bmin
+// ≥ dmax − B, cmax − a0 ≥ coh − a0, products of non-negatives), and a per-lane pair with
+// dmax − B < 0, c = 0 or a NaN anywhere fails on its own ("wave-level bound").
+template <int NP>
+__device__ __forceinline__ bool screen_wave(double dmax, double a0, double bmin, double cmax) {
+    const double cx[1] = {cmax - a0}, dd[1] = {dmax - bmin};
+    double t[1];
+    screen_t<NP, 1>(t, cx, dd);
+    return t[0] >= kThr;
+}
+
 template <bool LAB>
 __device__ __forceinline__ double cash(double x, double y, double Ll) {
     if constexpr (LAB) return x + y * Ll;  // (1+r)a_j + (w s_i) L_l   (Labor_VFI.m:81)

@@ -47,7 +47,10 @@ struct BellArgs {
     int* partial;   // [nlb][nchunk][N][Na] chunk improvements; -1 between sweeps
     int* touched;   // [N][Na] 1 when some chunk wrote `partial` for the state this sweep
     unsigned long long* hitcount;  // nullable, [4]: exact evals, superblock, block, fine tests
+                                   // (lane-level evaluations executed; the tree's wave-level
+                                   // superblock test counts its 64 lanes once)
     long long* trace;  // nullable: per tree work item {t0, t1, xcc, nsup, nblk, nfine, nhits, item}
+                       // (nsup: superblocks entered)
     // outputs
     double* v_new;
     int* idx;   // linear index l + Nl*k (== k for A1)

@@ -706,7 +706,8 @@ __global__ __launch_bounds__(256, MINW) void bell_screen_kernel(BellArgs A, int 
 // and searches all their candidates (every labour level, the whole feasible prefix) through a
 // bound tree, then writes the final outputs itself (no per-chunk partials, no merge pass).
 //   level 0: 512-candidate superblocks — bounds (Dmax512, a at the block start) fetched one
-//            superblock per lane in a single round trip and read back with v_readlane
+//            superblock per lane in a single round trip and tested there, once for the whole
+//            wave, against its lowest bar and its largest cash on hand (screen_wave)
 //   level 1/2: inside a passing superblock, one round trip fetches its 64 sub-block maxima
 //            (Dmax8) and sub-block starts; 64-blocks are their 8-lane butterfly maxima
 //   level 3: the candidates of every passing 64-block are staged in LDS together (one round
@@ -926,7 +927,9 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     }
     // nhits counts every exact evaluation of the launch: the start-up's (hint window,
     // extrapolated window, climb) and the screen's (VERDICT r4 "do this" 1)
-    unsigned nhits = nsu, nsup = 0, nblk = 0, nfine = 0, lane_pairs = 0;
+    // nsup: superblocks entered; nwv: wave-level tests of the level-0 bounds (64 lane
+    // evaluations each, whatever the number of sub-states)
+    unsigned nhits = nsu, nsup = 0, nwv = 0, nblk = 0, nfine = 0, lane_pairs = 0;
     const long long t_start = (INS && A.trace) ? (long long)wall_clock64() : 0;
     // phase cycle counters (trace mode): startup, superblock() calls, fine screens, exact paths
     long long cyc[4] = {0, 0, 0, 0}, c_mark = (INS && A.trace) ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -1286,32 +1289,51 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         } else {
             load512(0);
         }
-        // the passing superblocks in order: level-0 tests eight at a time, on demand
-        int g = 0, s8 = -8;
-        unsigned sm = 0;
+        // The wave's bar and cash: the minimum of its valid sub-states' bars (NaN bars drop out;
+        // idx < 0 gives −inf) and the maximum of their cash on hand, both wave-uniform.  Taken
+        // after the first superblock's exchange, so every wave holds the same, raised bar; the
+        // exact paths of the walk raise the lanes' bars further, and the older minimum stays a
+        // valid (only looser) bar.
+        double bmin, cmax;
+        {
+            double bl = __builtin_nan(""), cl = -__builtin_inf();
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int q = 0; q < LB; ++q) {
+                    bl = fmin(bl, B[r][q]);
+                    cl = fmax(cl, (okr[r] && l0 + q < Nl) ? coh[r][q] : -__builtin_inf());
+                }
+            bmin = wave_fmin_d(bl);
+            cmax = wave_fmax_d(cl);
+        }
+        // the passing superblocks in order: one wave-level test of the 64 level-0 bounds a
+        // group (screen_wave: lane u holds superblock g + u), balloted into a mask of this
+        // wave's superblocks (sb % W == wave, the first one excluded), walked bit by bit
+        int g = 0;
+        unsigned long long sm = 0;
+        auto test512 = [&]() __attribute__((always_inline)) {
+            if (INS) ++nwv;
+            unsigned long long m =
+                __ballot(lane < nsb - g && screen_wave<NP>(dm0, a0, bmin, cmax));
+            static_assert(64 % W == 0, "superblock g + u belongs to wave u % W");
+            if constexpr (W > 1) m &= (~0ull / ((1ull << W) - 1ull)) << wave;
+            if (sfirst >= g && sfirst < g + 64) m &= ~(1ull << (sfirst - g));
+            return m;
+        };
+        if (nsb > 0) sm = test512();
         auto next_sb = [&]() __attribute__((always_inline)) -> int {
             for (;;) {
                 if (sm) {
-                    const int u = __builtin_ctz(sm);
+                    const int u = __builtin_ctzll(sm);
                     sm &= sm - 1;
-                    return g + s8 + u;
+                    if (INS) ++nsup;
+                    return g + u;
                 }
-                s8 += 8;
-                if (s8 >= min(64, nsb - g)) {
-                    g += 64;
-                    s8 = 0;
-                    if (g >= nsb) return -1;
-                    load512(g);
-                }
-                const int cnt = min(8, min(64, nsb - g) - s8);
-                unsigned own = 0;
-                for (int u = 0; u < cnt; ++u) {
-                    const int sb = g + s8 + u;
-                    if (sb != sfirst && sb % W == wave) own |= 1u << u;
-                }
-                if (!own) continue;
-                if (INS) nsup += __builtin_popcount(own);
-                sm = mask8(dm0, a0, s8, 1, cnt) & own;
+                g += 64;
+                if (g >= nsb) return -1;
+                load512(g);
+                sm = test512();
             }
         };
         // software pipeline: load8 two superblocks ahead, the candidate loads one ahead
@@ -1426,7 +1448,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         if (nhits) atomicAdd(hc, (unsigned long long)nhits);
         if (lane == 0) {
             const unsigned long long ns = 64ull * R * LB;
-            atomicAdd(hc + 1, nsup * ns);
+            atomicAdd(hc + 1, nwv * 64ull);
             atomicAdd(hc + 2, nblk * ns);
             if (nfine) atomicAdd(hc + 3, nfine * ns);
         }
