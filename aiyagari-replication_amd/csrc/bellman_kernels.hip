@@ -730,7 +730,10 @@ __global__ __launch_bounds__(256, MINW) void bell_screen_kernel(BellArgs A, int 
 // HY (bell_tree_hybrid_kernel, variant bit 26): a two-wave workgroup runs either two one-wave
 // tiles (PK = 2) or one heavy tile with both waves (W = 2, with the one-wave pipelines: the
 // launch keeps the W = 1 register budget); s_cand / s_pass are the kernel's LDS, shared by both.
-template <int NP, bool LAB, int R, int LB, int W, bool INS, int PK, bool HY = false>
+// WM: the widest hint window half-width the body is compiled for — 1 when variant bits 7-8 are
+// clear (every production default: three window slots), 8 for the generic body (17 slots, each
+// a guarded load block and a guarded evaluation whatever the run-time width)
+template <int NP, bool LAB, int R, int LB, int W, bool INS, int PK, bool HY = false, int WM = 8>
 __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, int block_id,
                                                int nblocks, double2 (*s_cand)[512],
                                                unsigned long long* s_pass) {
@@ -775,7 +778,35 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     // stages four chains at a time; the best exchange reuses each wave's idle s_cand slice
     constexpr bool LEAN = (W >= 2 && !HY) || LAB;  // (labour: keeps 3 waves per SIMD)
 
-    // loads that do not depend on the start-up below, issued first so that their latency
+    // momentum (variant bit 9 clear): the argmax's shift over the last hinted sweep, so the
+    // start-up also tries hint + shift — in the early sweeps of a solve the optimum drifts by
+    // tens of candidates per sweep and a climb from the stale hint costs a dependent round
+    // trip per step.  Only the screening bar depends on it, never the result.
+    int* __restrict__ mom = (A.variant & kVarNoMomentum) ? nullptr : A.mom;
+    // One load round: everything the start-up reads per state has an address known from the
+    // item id alone — hint, momentum, the level-0 feasible prefix, a_j — so all of it is issued
+    // here, unconditionally and at a clamped in-range index, ahead of the loads the start-up
+    // does not wait for (below).  The conditions (h >= 0, kf > 0) select among the loaded
+    // values; around the loads they made each one a dependent round trip of its own.
+    // Only the three-slot body (WM = 1) does this: with the generic window the round gains
+    // nothing measurable and costs registers, so that body loads
+    // each value where it is used, as before.
+    constexpr bool PRE = WM == 1;
+    int h_pre[R], m_pre[R], kf_pre[R];
+    double aj_pre[R];
+    if constexpr (PRE) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int j = jbase + r * 64 + lane;
+            const int jc = (j < Na && r * 64 + lane < TW) ? j : 0;
+            const size_t t = (size_t)i * Na + jc;
+            h_pre[r] = A.hint ? A.hint[t] : -1;
+            m_pre[r] = (A.hint && mom) ? mom[t] : 0;
+            kf_pre[r] = A.kf[t];
+            aj_pre[r] = a[jc];
+        }
+    }
+    // loads that do not depend on the start-up below, issued with it so that their latency
     // overlaps it: the level-0 bounds of the first 64 superblocks (first labour group) and v_old
     double dm0_pre, a0_pre;
     {
@@ -793,36 +824,38 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     double x[R], best[R];
     int idx[R], hk0[R], mlast[R];  // mlast: the last sweep's shift (packed into mom's high half)
     bool okr[R], feas[R];
-    // momentum (variant bit 9 clear): the argmax's shift over the last hinted sweep, so the
-    // start-up also tries hint + shift — in the early sweeps of a solve the optimum drifts by
-    // tens of candidates per sweep and a climb from the stale hint costs a dependent round
-    // trip per step.  Only the screening bar depends on it, never the result.
-    int* __restrict__ mom = (A.variant & kVarNoMomentum) ? nullptr : A.mom;
     unsigned nsu = 0;  // (instrumentation) the start-up's exact evaluations: window + climb
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int j = jbase + r * 64 + lane;
         okr[r] = j < Na && r * 64 + lane < TW;
         const size_t t = (size_t)i * Na + (okr[r] ? j : 0);
-        x[r] = okr[r] ? (1 + A.r) * a[j] : 0.0;
+        if constexpr (PRE) x[r] = okr[r] ? (1 + A.r) * aj_pre[r] : 0.0;
+        else x[r] = okr[r] ? (1 + A.r) * a[j] : 0.0;
         best[r] = __builtin_nan("");
         idx[r] = -1;
         hk0[r] = -1;
         mlast[r] = 0;
         feas[r] = false;
         if (!okr[r]) continue;
-        for (int l = 0; l < Nl; ++l) feas[r] = feas[r] || A.kf[l * nall + t] > 0;
+        if constexpr (PRE) feas[r] = kf_pre[r] > 0;
+        for (int l = PRE ? 1 : 0; l < Nl; ++l) feas[r] = feas[r] || A.kf[l * nall + t] > 0;
         if (A.hint) {
-            const int h = A.hint[t];
+            int h;
+            if constexpr (PRE) h = h_pre[r];
+            else h = A.hint[t];
             // mom packs two shifts: low 16 bits the last sweep's, high 16 the one before; with
             // variant bit 21 the start extrapolates the drift linearly (2·last − previous)
-            const int mraw = (mom && h >= 0) ? mom[t] : 0;
+            int mraw = 0;
+            if constexpr (PRE) mraw = h >= 0 ? m_pre[r] : 0;
+            else mraw = (mom && h >= 0) ? mom[t] : 0;
             const int ms0 = (int)(short)(mraw & 0xffff), ms1 = (int)(short)(mraw >> 16);
             mlast[r] = ms0;
             const int mv = max(-Na, min(Na, (A.variant & kVarDriftExtrap) ? 2 * ms0 - ms1 : ms0));
             if (h >= 0) {
                 const int hl = h % Nl;
-                const int kf = A.kf[hl * nall + t];
+                // (A1: Nl = 1, so the hint's level is 0 and its prefix is already here)
+                const int kf = (PRE && hl == 0) ? kf_pre[r] : A.kf[hl * nall + t];
                 if (kf > 0) {
                     const int hk = min(h / Nl, kf - 1);
                     const double coh = cash<LAB>(x[r], y, LAB ? A.L[hl] : 1.0);
@@ -836,7 +869,8 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     // variant bits 7-8), all loads in flight together, then their exact values
                     // (independent chains).  Indices are clamped into the feasible prefix; a
                     // repeated candidate merges as a no-op.
-                    const int wn = 1 << ((A.variant & kVarHintWinMask) >> kVarHintWinShift);
+                    const int wn =
+                        WM == 1 ? 1 : 1 << ((A.variant & kVarHintWinMask) >> kVarHintWinShift);
                     hk0[r] = hk;
                     // the extrapolated start hm = hint + last shift and its two neighbours,
                     // when that window does not touch the hint's own
@@ -849,7 +883,6 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     // bit 24 (with 23): not even the hint itself — the extrapolated window
                     // and the climb from it carry the start alone
                     const bool skiph = usem && (A.variant & kVarNoHintEval);
-                    constexpr int WM = 8;
                     double wa[2 * WM + 1], we[2 * WM + 1], ma[3], me[3];
 #pragma unroll
                     for (int d = -WM; d <= WM; ++d) {
@@ -1455,7 +1488,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     }
 }
 
-template <int NP, bool LAB, int R, int LB, int W, bool INS, int PK>
+template <int NP, bool LAB, int R, int LB, int W, bool INS, int PK, int WM>
 // min waves per SIMD 3 (168 VGPRs): every item of Na = 20,000 is resident at W = 1; the
 // cooperative tiles (W >= 2) serve small grids and labour, where a few hundred waves run and
 // latency, not occupancy, bounds them — a budget of 5 (and of 4) made those builds spill
@@ -1463,8 +1496,8 @@ __global__ __launch_bounds__(64 * W * PK, 3) void bell_tree_kernel(BellArgs A0, 
     __shared__ double2 s_cand[W * PK][512];
     __shared__ unsigned long long s_pass[W];
     const int lw = PK > 1 ? readfirst(threadIdx.x >> 6) : 0;
-    bell_tree_item<NP, LAB, R, LB, W, INS, PK>(A0, ntile, (int)blockIdx.x * PK + lw,
-                                               (int)gridDim.x * PK, s_cand, s_pass);
+    bell_tree_item<NP, LAB, R, LB, W, INS, PK, false, WM>(A0, ntile, (int)blockIdx.x * PK + lw,
+                                                          (int)gridDim.x * PK, s_cand, s_pass);
 }
 
 // Heavy tiles on two waves (variant bit 26, A1 with a dispatch permutation): workgroup b holds
@@ -1720,17 +1753,27 @@ static void run_screen(const BellArgs& A, hipStream_t st) {
         }
     }
 }
-template <int NP, bool LAB, int R, int W, int PK = 1>
-static void tree_geo(const BellArgs& A, hipStream_t st) {
+template <int NP, bool LAB, int R, int W, int PK, int WM>
+static void tree_geo_w(const BellArgs& A, hipStream_t st) {
     constexpr int LB = LAB ? 5 : 1;
     const int ntile = cdiv(A.Na, bell_tile_width(A, R));
     const int grid = cdiv(std::max(A.C, 1) * A.N * ntile, PK);
     if (A.trace || A.hitcount)
-        launch_dispatch_timed(bell_tree_kernel<NP, LAB, R, LB, W, true, PK>, dim3(grid),
+        launch_dispatch_timed(bell_tree_kernel<NP, LAB, R, LB, W, true, PK, WM>, dim3(grid),
                               dim3(64 * W * PK), 0, st, A, ntile);
     else
-        launch_dispatch_timed(bell_tree_kernel<NP, LAB, R, LB, W, false, PK>, dim3(grid),
+        launch_dispatch_timed(bell_tree_kernel<NP, LAB, R, LB, W, false, PK, WM>, dim3(grid),
                               dim3(64 * W * PK), 0, st, A, ntile);
+}
+// the hint window's compile-time width: variant bits 7-8 clear (every default) -> the three-slot
+// body; set (tuning) -> the generic 17-slot one.  Like the tuning geometries, the second body is
+// instantiated for the reference sigma = 5 (NP = 4) only: other sigmas keep the one generic body
+template <int NP, bool LAB, int R, int W, int PK = 1>
+static void tree_geo(const BellArgs& A, hipStream_t st) {
+    if constexpr (NP == 4) {
+        if (!(A.variant & kVarHintWinMask)) return tree_geo_w<NP, LAB, R, W, PK, 1>(A, st);
+    }
+    tree_geo_w<NP, LAB, R, W, PK, 8>(A, st);
 }
 // variant bit 0: 2 states per lane (A1 only); bits 1-2: waves per tile 1 (default), 2, 4, 8;
 // one-wave tiles with a dispatch permutation: bell_tree_pack waves per workgroup
