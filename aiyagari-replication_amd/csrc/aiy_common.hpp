@@ -197,8 +197,10 @@ __device__ __forceinline__ void block_max_to_slots(bool ok, double d,
 // the same for a one-wave workgroup: the wave's maximum goes straight from lane 0 to the slot —
 // no LDS, no workgroup barrier (whose release fence would make the wave wait for all of its
 // output stores before the atomics could issue)
+// (`blk`: the workgroup's index among those sharing the slot set, blockIdx.x unless given)
 __device__ __forceinline__ void wave_max_to_slots(bool ok, double d,
-                                                  unsigned long long* __restrict__ slots) {
+                                                  unsigned long long* __restrict__ slots,
+                                                  int blk) {
     unsigned long long key = ok ? (unsigned long long)aiy_dbits(d) : 0ull;
     const bool any = __ballot(ok) != 0ull;
     key = wave_max_u64_lane63(key);
@@ -206,10 +208,14 @@ __device__ __forceinline__ void wave_max_to_slots(bool ok, double d,
     const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(key >> 32), 63);
     key = ((unsigned long long)hi << 32) | lo;
     if (any && (threadIdx.x & 63) == 0) {
-        unsigned long long* sl = slots + 2 * (blockIdx.x % kDiffSlots);
+        unsigned long long* sl = slots + 2 * ((unsigned)blk % kDiffSlots);
         atomicMax(sl, key);
         atomicOr(sl + 1, 1ull);
     }
+}
+__device__ __forceinline__ void wave_max_to_slots(bool ok, double d,
+                                                  unsigned long long* __restrict__ slots) {
+    wave_max_to_slots(ok, d, slots, (int)blockIdx.x);
 }
 
 inline int is_int_ge(double x, double lo) {

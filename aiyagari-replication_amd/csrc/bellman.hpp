@@ -59,9 +59,14 @@ struct BellArgs {
     double* pc;
     unsigned long long* diff;  // nullable, [2]
     unsigned long long* fold;  // nullable [2]: the table kernel folds the previous sweep's diff slots here
-    // batched candidate rates (config 4; A1 tree screen only).  C <= 1: a single candidate.
-    // C > 1: every per-state array above is C consecutive blocks of its single layout, diff is
-    // [C][2][2*kDiffSlots] (parity = sweep & 1 selects the set this sweep writes).
+    // batched candidate rates.  C <= 1: a single candidate.  C > 1: every per-state array above
+    // is C consecutive blocks of its single layout (v_old, v_new, idx, pk, pl, pc, hint
+    // [C][N][Na]; kf [C][Nl][N][Na]; L and dis shared), r and w come from rv[c], wv[c].  Two
+    // paths take it: config 4's A1 tree screen (bell_solve_batch_dev: diff is
+    // [C][2][2*kDiffSlots], parity = sweep & 1 selects the set this sweep writes, `stop` read
+    // by its kernels) and the labour small-grid sweep (bell_labor_solve_batch_dev →
+    // launch_bell_wide_batch, which takes its three slot sets per candidate and the stop flags
+    // as launch arguments: wide_batch.hpp).  launch_bell_kf serves both.
     int C;
     bool ev_mfma;      // EV = (βP)·V by fp64 MFMA (bell_ev_mfma_kernel) before the table kernel
     const double* rv;  // [C] device: r of each candidate
@@ -183,6 +188,12 @@ constexpr size_t kExclusiveLds = 88 * 1024;
 int launch_bell_wide(const BellArgs& A, int S, int NW, int SB, unsigned long long* old_slots,
                      unsigned* cnt, unsigned long long* part, int flags, size_t min_lds,
                      hipStream_t st);
+// The same sweep for labour at A.C candidate rates (bellman_wide_batch_kernels.hip): sweep
+// `sweep` (1-based) of every candidate whose stop[c] is 0 and whose previous sweep's
+// max|Δv| (slots [C][3][2*kDiffSlots], wide_batch.hpp) is not below tol; a candidate found
+// below tol gets stop[c] = sweep - 1 and is left untouched from then on.
+int launch_bell_wide_batch(const BellArgs& A, int NW, int SB, unsigned long long* slots, int* stop,
+                           int sweep, double tol, int flags, size_t min_lds, hipStream_t st);
 int launch_bell_ev_mfma(const BellArgs& A, hipStream_t st);
 int launch_bell_table(const BellArgs& A, hipStream_t st);
 int launch_bell_kf(const BellArgs& A, hipStream_t st);

@@ -14,6 +14,7 @@
 
 #include "aiy_common.hpp"
 #include "tree_perm.hpp"
+#include "wide_batch.hpp"
 #include "ws.hpp"
 
 namespace aiy {
@@ -720,6 +721,143 @@ int bell_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w
     return AIY_OK;
 }
 
+// A3 at C candidate rates (one GE round of Aiyagari_Endogenous_Labor_VFI.m:166-219): each
+// candidate the loop :64-122 from its own v_old / incoming v_new / policies, all candidates still
+// running in ONE small-grid launch per sweep (bellman_wide_batch_kernels.hip).  The kernel runs
+// each candidate's :115-118 test on the device (it folds the candidate's previous slot set and
+// freezes the candidate), so iteration counts, v_new, v_old and policies are those of C separate
+// solves.  Buffers as bell_solve_batch_dev: sweep g reads buf[(g-1) & 1] and writes buf[g & 1]
+// with buf[0] = v_a, so v_b holds every candidate's incoming v_new for sweep 1's keep-incoming
+// rule (:85), and a candidate that stopped at g* holds v_new in buf[g* & 1].  The host reads the
+// stop flags once per `spec_max` sweeps.  Shapes the one-launch sweep does not take (wide_pick)
+// and C below the workspace's threshold run one bell_solve_dev after another.
+int bell_labor_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                               double* v_a, double* v_b, const double* a, const double* s,
+                               const double* P, const double* L, double beta, double sigma,
+                               double psi, double eta, double tol, int64_t max_iter, int use_hint,
+                               int* lin, double* pk, double* pl, double* pc, int64_t* iters,
+                               int* which, hipStream_t st) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (!r || !w || !v_a || !v_b || v_a == v_b || !a || !s || !P || !L || !lin || !iters || !which)
+        return fail(AIY_BAD_ARG, "NULL argument (or v_a == v_b)");
+    if (C < 1 || C > (1 << 20)) return fail(AIY_BAD_SHAPE, "need 1 <= C <= 2^20 candidates");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    for (int64_t c = 0; c < C; ++c)
+        if (!std::isfinite(r[c]) || !std::isfinite(w[c]))
+            return fail(AIY_NON_FINITE, "candidate %lld: non-finite r or w", (long long)c + 1);
+    if (!(beta == beta) || !(sigma == sigma) || !(psi == psi) || !(eta == eta) || !(tol == tol))
+        return fail(AIY_NON_FINITE, "non-finite scalar argument");
+    const size_t n = (size_t)ws->N * ws->Na;
+    const int64_t Nl = ws->Nl;
+    if ((size_t)C * (size_t)Nl * n > (size_t)INT32_MAX)
+        return fail(AIY_BAD_SHAPE, "C*Nl*N*Na must fit int32");
+    BellArgs A{};
+    A.N = (int)ws->N; A.Na = (int)ws->Na; A.Nl = (int)Nl; A.labor = true;
+    A.np = is_int_ge(sigma, 2.0) && sigma <= 9.0 ? (int)sigma - 1 : 0;
+    A.ev_mfma = bell_ev_mfma(A.N, ws->variant);
+    int wS = 0, wNW = 0, wSB = 0;
+    const int64_t min_c = ws->labor_batch_min > 0 ? ws->labor_batch_min : kLaborBatchMinC;
+    if (C < min_c || !wide_pick(ws, A, &wS, &wNW, &wSB)) {
+        for (int64_t c = 0; c < C; ++c) {
+            BellCall bc{};
+            bc.labor = true; bc.Nl = Nl; bc.L = L; bc.psi = psi; bc.eta = eta;
+            bc.a = a; bc.s = s; bc.P = P; bc.r = r[c]; bc.w = w[c]; bc.beta = beta;
+            bc.sigma = sigma; bc.idx = lin + c * n; bc.pk = pk ? pk + c * n : nullptr;
+            bc.pl = pl ? pl + c * n : nullptr; bc.pc = pc ? pc + c * n : nullptr;
+            bc.hint = use_hint ? lin + c * n : nullptr;
+            AIY_TRY(bell_solve_dev(ws, bc, v_a + c * n, v_b + c * n, tol, max_iter, &iters[c],
+                                   &which[c], st));
+            ++ws->labor_batch_fallbacks;
+        }
+        AIY_HIP(hipStreamSynchronize(st));
+        return AIY_OK;
+    }
+    LaborBatchBlocks& bb = ws->labor_batch;
+    if (bb.C != C) {
+        bb = LaborBatchBlocks{};
+        AIY_TRY(bb.kf.ensure((size_t)C * Nl * n));
+        AIY_TRY(bb.stop.ensure((size_t)C));
+        AIY_TRY(bb.slots.ensure(wide_batch_set_off(C, 0, kDiffSlots)));
+        AIY_TRY(bb.rw.ensure(2 * (size_t)C));
+        AIY_TRY(bb.hstop.ensure((size_t)C));
+        AIY_TRY(bb.hslots.ensure((size_t)C * 2 * kDiffSlots));
+        bb.C = C;
+    }
+    AIY_TRY(ws_ensure_bell(ws, 1));  // dis / hitcount scratch and events (single-rate buffers)
+    AIY_HIP(hipMemcpyAsync(bb.rw, r, C * sizeof(double), hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemcpyAsync(bb.rw + C, w, C * sizeof(double), hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemsetAsync(bb.stop, 0, C * sizeof(int), st));
+    AIY_HIP(hipMemsetAsync(bb.slots, 0,
+                           wide_batch_set_off(C, 0, kDiffSlots) * sizeof(unsigned long long), st));
+    if (!(ws->dis_ok && ws->dis_L == L && ws->dis_Nl == Nl && ws->dis_psi == psi &&
+          ws->dis_eta == eta)) {
+        AIY_TRY(launch_disutility(L, (int)Nl, psi, eta, ws->dis, st));
+        ws->dis_ok = true;
+        ws->dis_L = L; ws->dis_Nl = Nl; ws->dis_psi = psi; ws->dis_eta = eta;
+    }
+    A.beta = beta; A.sigma = sigma; A.a = a; A.s = s; A.P = P; A.L = L; A.dis = ws->dis;
+    A.r = r[0]; A.w = w[0];  // (C = 1: the kf kernel reads these)
+    A.kf = bb.kf;
+    A.hitcount = ws->count_hits ? ws->hitcount : nullptr;
+    A.idx = lin; A.pk = pk; A.pl = pl; A.pc = pc;
+    A.C = (int)C; A.rv = bb.rw; A.wv = bb.rw + C; A.stop = bb.stop;
+    AIY_TRY(launch_bell_kf(A, st));  // per-candidate feasible prefixes, once per solve
+    const char* fl = getenv("AIY_WIDE_FLAGS");  // (A/B tooling: tools/wide_tune.py)
+    const int flags = fl ? atoi(fl) : kWideDefaultFlags;
+    double* buf[2] = {v_a, v_b};
+    int64_t g = 0;
+    bool all_stopped = false;
+    const int64_t m = std::max(ws->spec_max, 1);
+    while (!all_stopped && g < max_iter) {
+        const int64_t gend = std::min(max_iter, g + m);
+        for (++g; g <= gend; ++g) {
+            A.v_old = buf[(g - 1) & 1];
+            A.v_new = buf[g & 1];
+            A.keep_incoming = (g == 1);
+            A.hint = (g == 1 && !use_hint) ? nullptr : lin;
+            AIY_TRY(ws_dispatch_arm(ws));
+            const int rc = launch_bell_wide_batch(A, wNW, wSB, bb.slots, bb.stop, (int)g, tol,
+                                                  flags, ws->cu_exclusive ? kExclusiveLds : 0, st);
+            ws_dispatch_commit(ws);
+            AIY_TRY(rc);
+        }
+        --g;  // sweeps launched so far
+        AIY_HIP(hipMemcpyAsync(bb.hstop, bb.stop, C * sizeof(int), hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipStreamSynchronize(st));
+        all_stopped = true;
+        for (int64_t c = 0; c < C; ++c) all_stopped = all_stopped && bb.hstop[c] != 0;
+    }
+    // candidates still running after the last sweep G: fold their sweep-G slots (its :115
+    // test), else the loop was exhausted and v_old = v_new (:120)
+    const int64_t G = g;
+    bool any_running = false;
+    for (int64_t c = 0; c < C; ++c) any_running = any_running || bb.hstop[c] == 0;
+    if (any_running) {
+        for (int64_t c = 0; c < C; ++c)
+            if (bb.hstop[c] == 0)
+                AIY_HIP(hipMemcpyAsync(
+                    bb.hslots + c * 2 * kDiffSlots,
+                    bb.slots + wide_batch_set_off(c, wide_batch_write_set(G), kDiffSlots),
+                    2 * kDiffSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipStreamSynchronize(st));
+    }
+    for (int64_t c = 0; c < C; ++c) {
+        int64_t it = bb.hstop[c];
+        if (it == 0) {
+            const double d = fold_slots_host(bb.hslots + c * 2 * kDiffSlots);
+            it = G;
+            if (!(d < tol))  // exhausted: v_old = v_new after the last sweep
+                AIY_HIP(hipMemcpyAsync(buf[(G - 1) & 1] + c * n, buf[G & 1] + c * n,
+                                       n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        iters[c] = it;
+        which[c] = (int)(it & 1);
+    }
+    AIY_HIP(hipStreamSynchronize(st));
+    ++ws->labor_batch_solves;
+    return AIY_OK;
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -918,6 +1056,32 @@ int aiy_vfi_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double
     return bell_solve_batch_dev(ws, C, r, w, v_a, v_b, a_grid, s, P, beta, sigma, tol, max_iter,
                                 use_hint, idx, policy_k, policy_c, iters, which,
                                 (hipStream_t)stream);
+}
+
+int aiy_labor_vfi_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                                  double* v_a, double* v_b, const double* a_grid,
+                                  const double* s, const double* P, const double* labor_choice,
+                                  double beta, double sigma, double psi, double eta, double tol,
+                                  int64_t max_iter, int use_hint, int32_t* lin, double* policy_k,
+                                  double* policy_l, double* policy_c, int64_t* iters,
+                                  int32_t* which, void* stream) {
+    return bell_labor_solve_batch_dev(ws, C, r, w, v_a, v_b, a_grid, s, P, labor_choice, beta,
+                                      sigma, psi, eta, tol, max_iter, use_hint, lin, policy_k,
+                                      policy_l, policy_c, iters, which, (hipStream_t)stream);
+}
+
+int aiy_ws_set_labor_batch(aiy_ws* ws, int min_candidates) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (min_candidates < 0) return fail(AIY_BAD_ARG, "min_candidates >= 0 (0: the default)");
+    ws->labor_batch_min = min_candidates;
+    return AIY_OK;
+}
+
+int aiy_ws_labor_batch_counts(aiy_ws* ws, int64_t* batched_solves, int64_t* fallback_solves) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (batched_solves) *batched_solves = ws->labor_batch_solves;
+    if (fallback_solves) *fallback_solves = ws->labor_batch_fallbacks;
+    return AIY_OK;
 }
 
 int aiy_labor_vfi_sweep_dev(aiy_ws* ws, const double* v_old, const double* a_grid,

@@ -36,7 +36,7 @@ struct GeShare {
 // one host thread per device when there are several.  Holds the host-tier lock; the first
 // failing share's status and message are the call's.
 template <class Body>
-int ge_run_shares(int64_t C, int64_t N, int64_t Na, int n_devices, Body body) {
+int ge_run_shares(int64_t C, int64_t N, int64_t Na, int64_t Nl, int n_devices, Body body) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(AIY_NO_DEVICE, "no HIP device visible");
@@ -50,7 +50,7 @@ int ge_run_shares(int64_t C, int64_t N, int64_t Na, int n_devices, Body body) {
         sh[d].c0 = d * (C / nd) + std::min<int64_t>(d, C % nd);
         sh[d].cn = C / nd + (d < C % nd ? 1 : 0);
         (void)hipSetDevice(sh[d].dev);
-        int rc = get_ctx(N, Na, 1, &sh[d].ctx);
+        int rc = get_ctx(N, Na, Nl, &sh[d].ctx);
         if (rc != AIY_OK) {
             (void)hipSetDevice(cur);
             return rc;
@@ -201,6 +201,51 @@ static int egm_ge_share(GeShare& sh, const double* r, const double* w, const dou
     return AIY_OK;
 }
 
+// one device's share of aiy_labor_ge_batch: every candidate from the common v_old, incoming
+// v_new, policies and index (rows[0..4] [N][Na] doubles, lin0 0-based), the batched labour solve
+// at the candidate's own wage, the chains on policy_k
+static int labor_ge_share(GeShare& sh, const double* r, const double* const rows[5],
+                          const int* lin0, const double* a, const double* s, const double* P,
+                          const double* L, int64_t N, int64_t Na, int64_t Nl, double alpha,
+                          double delta, double beta, double sigma, double psi, double eta,
+                          double tol, int64_t max_iter, int64_t z1, double k1, int64_t T,
+                          const double* uniforms, double* k_supply, int64_t* iters) {
+    AIY_HIP(hipSetDevice(sh.dev));
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    double *da, *ds, *dP, *dL, *dU, *d[5];  // d: v_a, v_b, policy_k, policy_l, policy_c
+    int* lin;
+    AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
+    AIY_TRY(c->buf("L", sizeof(double) * Nl, (void**)&dL));
+    AIY_HIP(hipMemcpyAsync(dL, L, sizeof(double) * Nl, hipMemcpyHostToDevice, c->st));
+    static const char* const names[5] = {"lge_va", "lge_vb", "ge_pk", "lge_pl", "lge_pc"};
+    for (int q = 0; q < 5; ++q) {
+        AIY_TRY(c->buf(names[q], nb * C, (void**)&d[q]));
+        AIY_HIP(hipMemcpyAsync(d[q], rows[q], nb, hipMemcpyHostToDevice, c->st));
+        for (int64_t k = 1; k < C; ++k)
+            AIY_HIP(hipMemcpyAsync(d[q] + k * n, d[q], nb, hipMemcpyDeviceToDevice, c->st));
+    }
+    AIY_TRY(c->buf("ge_idx", sizeof(int) * n * C, (void**)&lin));
+    AIY_HIP(hipMemcpyAsync(lin, lin0, sizeof(int) * n, hipMemcpyHostToDevice, c->st));
+    for (int64_t k = 1; k < C; ++k)
+        AIY_HIP(hipMemcpyAsync(lin + k * n, lin, sizeof(int) * n, hipMemcpyDeviceToDevice, c->st));
+    AIY_TRY(ge_stage_uniforms(sh, T, uniforms, &dU));
+    std::vector<double> w(C);
+    for (int64_t q = 0; q < C; ++q)  // Aiyagari_Endogenous_Labor_VFI.m:173 (w at the candidate r)
+        w[q] = (1 - alpha) * std::pow(alpha / (r[sh.c0 + q] + delta), alpha / (1 - alpha));
+    std::vector<int> which(C);
+    AIY_TRY(bell_labor_solve_batch_dev(c->ws, C, r + sh.c0, w.data(), d[0], d[1], da, ds, dP, dL,
+                                       beta, sigma, psi, eta, tol, max_iter, 0, lin, d[2], d[3],
+                                       d[4], iters + sh.c0, which.data(), c->st));
+    std::vector<int> status(C);
+    AIY_TRY(ge_chains(sh, d[2], da, dP, dU, N, Na, z1, k1, T, nullptr, k_supply, status.data()));
+    for (int64_t q = 0; q < C; ++q)
+        if (status[q]) return fail(AIY_FIND_EMPTY, "candidate %lld: find(rand < cumsum(P(z,:))) empty",
+                                   (long long)(sh.c0 + q + 1));
+    return AIY_OK;
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -224,11 +269,59 @@ int aiy_ge_batch(const double* r, int64_t C, const double* v_start, const double
             return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
     std::vector<double> rows((size_t)N * Na);
     cm_to_rows(v_start, N, Na, rows.data());
-    AIY_TRY(ge_run_shares(C, N, Na, n_devices, [&](GeShare& g) {
+    AIY_TRY(ge_run_shares(C, N, Na, 1, n_devices, [&](GeShare& g) {
         return ge_share(g, r, rows.data(), a_grid, s, P, N, Na, alpha, delta, beta, sigma, tol,
                         max_iter, z1, k1, T, uniforms, k_supply, iters);
     }));
     for (int64_t q = 0; q < C; ++q)  // Aiyagari_VFI.m:195
+        k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
+    return AIY_OK;
+}
+
+int aiy_labor_ge_batch(const double* r, int64_t C, const double* v_start,
+                       const double* v_new_start, const double* policy_k_start,
+                       const double* policy_l_start, const double* policy_c_start,
+                       const int32_t* policy_lin_start, const double* a_grid, const double* s,
+                       const double* P, const double* labor_choice, int64_t N, int64_t Na,
+                       int64_t Nl, double alpha, double delta, double beta, double sigma,
+                       double psi, double eta, double labor, double tol, int64_t max_iter,
+                       int64_t z1, double k1, int64_t T, const double* uniforms, int n_devices,
+                       double* k_supply, double* k_demand, int64_t* iters) {
+    if (!r || !v_start || !s || !P || !labor_choice || !k_supply || !k_demand || !iters ||
+        (T > 1 && !uniforms))
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || N < 1 || Na < 2 || Nl < 1)
+        return fail(AIY_BAD_SHAPE, "need C >= 1, N >= 1, Na >= 2, Nl >= 1");
+    if (T < 1 || T > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "T must be in [1, 2^31)");
+    if (z1 < 1 || z1 > N) return fail(AIY_BAD_ARG, "z1 (1-based) out of range");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    if (!(std::isfinite(psi) && std::isfinite(eta)))
+        return fail(AIY_NON_FINITE, "psi and eta must be finite");
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    for (int64_t q = 0; q < C; ++q)
+        if (!std::isfinite(r[q]) || r[q] + delta <= 0)
+            return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
+    // the common start, N x Na column-major -> [N][Na]; a NULL start is zeros (index: 1)
+    const size_t n = (size_t)N * Na;
+    const double* const cm[5] = {v_start, v_new_start, policy_k_start, policy_l_start,
+                                 policy_c_start};
+    std::vector<double> rows[5];
+    const double* rp[5];
+    for (int q = 0; q < 5; ++q) {
+        rows[q].assign(n, 0.0);
+        if (cm[q]) cm_to_rows(cm[q], N, Na, rows[q].data());
+        rp[q] = rows[q].data();
+    }
+    std::vector<int> lin0(n, 0);
+    if (policy_lin_start)
+        for (int64_t j = 0; j < Na; ++j)
+            for (int64_t i = 0; i < N; ++i) lin0[i * Na + j] = policy_lin_start[i + j * N] - 1;
+    AIY_TRY(ge_run_shares(C, N, Na, Nl, n_devices, [&](GeShare& g) {
+        return labor_ge_share(g, r, rp, lin0.data(), a_grid, s, P, labor_choice, N, Na, Nl, alpha,
+                              delta, beta, sigma, psi, eta, tol, max_iter, z1, k1, T, uniforms,
+                              k_supply, iters);
+    }));
+    for (int64_t q = 0; q < C; ++q)  // Aiyagari_Endogenous_Labor_VFI.m:239
         k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
     return AIY_OK;
 }
@@ -254,7 +347,7 @@ int aiy_egm_ge_batch(const double* r, const double* w, int64_t C, const double* 
     for (int64_t q = 0; q < C; ++q)
         if (!std::isfinite(r[q]) || r[q] + delta <= 0)
             return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
-    AIY_TRY(ge_run_shares(C, N, Na, n_devices, [&](GeShare& g) {
+    AIY_TRY(ge_run_shares(C, N, Na, 1, n_devices, [&](GeShare& g) {
         return egm_ge_share(g, r, w, policy_c_start, a_grid, s, P, N, Na, beta, sigma, amin,
                             labor_flag, phi, theta, tol, max_iter, z1, k1, T, uniforms, k_supply,
                             iters, status);

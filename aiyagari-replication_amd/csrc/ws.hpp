@@ -57,6 +57,17 @@ struct BatchBlocks {
     PinnedBuf<int> hstop;   // [C]
     PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
 };
+// batched labour solve on the small-grid sweep (aiy_labor_vfi_solve_batch_dev): per-candidate
+// feasible prefixes, stop flags, three slot sets each (wide_batch.hpp), sized for C candidates
+struct LaborBatchBlocks {
+    int64_t C = 0;
+    DevBuf<int> kf;         // device [C][Nl][N][Na]
+    DevBuf<int> stop;       // device [C]
+    DevBuf<u64> slots;      // device [C][3][2*kDiffSlots]
+    DevBuf<double> rw;      // device [2][C]: r then w
+    PinnedBuf<int> hstop;   // [C]
+    PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
+};
 }  // namespace aiy
 
 struct aiy_ws {
@@ -139,6 +150,12 @@ struct aiy_ws {
     int egm_batch_min = -1;
     aiy::EgmBatchBlocks egm_batch;
     int64_t egm_batch_launches = 0, egm_batch_fallbacks = 0;
+    // batched multi-rate labour VFI solve (aiy_labor_vfi_solve_batch_dev; aiy_ws_set_labor_batch):
+    // one launch per sweep over all candidates from labor_batch_min candidates on (0: the
+    // default, kLaborBatchMinC), its blocks, and how often each path ran on this workspace
+    int labor_batch_min = 0;
+    aiy::LaborBatchBlocks labor_batch;
+    int64_t labor_batch_solves = 0, labor_batch_fallbacks = 0;
     // timing of the dominant kernel
     bool timing = false, count_hits = false;
     aiy::Events ev_start, ev_stop;
@@ -190,6 +207,17 @@ int bell_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w
                          double beta, double sigma, double tol, int64_t max_iter, int use_hint,
                          int* idx, double* pk, double* pc, int64_t* iters, int* which,
                          hipStream_t st);
+// A3 at C candidate rates: one small-grid launch per sweep over all candidates still running
+// where the shape takes the one-launch sweep and C reaches the workspace's threshold, else one
+// bell_solve_dev after another (same results).  Arrays as BellArgs' batch layout; r, w, iters,
+// which: host [C].
+constexpr int kLaborBatchMinC = 2;  // default dispatch threshold
+int bell_labor_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                               double* v_a, double* v_b, const double* a, const double* s,
+                               const double* P, const double* L, double beta, double sigma,
+                               double psi, double eta, double tol, int64_t max_iter, int use_hint,
+                               int* lin, double* pk, double* pl, double* pc, int64_t* iters,
+                               int* which, hipStream_t st);
 int launch_reduce_slots(const unsigned long long* slots, void* out, hipStream_t st);
 double fold_slots_host(const unsigned long long* h);
 int launch_disutility(const double* L, int Nl, double psi, double eta, double* dis,

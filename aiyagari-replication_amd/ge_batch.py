@@ -419,3 +419,143 @@ def aiyagari_egm_multisection(Na=400, labor=False, levels=None, rank=0, world=1,
                       allgather=allgather)
     tr.iters = [int(R0["iters"])] + tr.iters
     return tr
+
+
+# ------------------------------------------------------- the labour VFI script (E2)
+def labor_calibration(Na=400):
+    """Aiyagari_Endogenous_Labor_VFI.m's calibration (rho = .6, sigma_e = .2) and its 10 labour
+    levels."""
+    from . import calibration as cb
+    cal = cb.aiyagari(Na=Na, rho=0.6, sigma_e=0.2)
+    return cal, 0.01 + (1.5 - 0.01) * cb.linspace01(10)
+
+
+def labor_start(R):
+    """The state the script carries from one solve into the next (and a state with no feasible
+    choice keeps, :85), from a labour solve's result: v_old, v_new and the policies."""
+    return dict(v_old=R["v_old"], v_new=R["v_new"],
+                policies=(R["policy_k"], R["policy_l"], R["policy_c"], R["lin"]))
+
+
+def labor_vfi_evaluator(cal, solve, simulate, start, T=10000):
+    """Node evaluator for Aiyagari_Endogenous_Labor_VFI.m:166-245: the labour VFI from `start`
+    (labor_start: the path-independent warm start) at the node's r and its own wage, MC supply on
+    policy_k with the uniforms block of the node's depth, K_d.  Generic in the two callables (the
+    GPU path or the C oracle): solve(start, r, w) -> dict(policy_k, iters);
+    simulate(policy_k, z1, k1, uniforms) -> K_s."""
+    from . import calibration as cb
+    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
+    head, blocks = mc_stream(T)
+    z1 = int(math.ceil(N * head[0]))
+    k1 = a[int(math.ceil(Na * head[1])) - 1]
+
+    def evaluate(node):
+        r = node.r
+        R = solve(start, r, cb.wage(r, cal["alpha"], cal["delta"]))
+        Ks = simulate(R["policy_k"], z1, k1, blocks[node.depth])
+        Kd = cb.capital_demand(r, cal["labor"], cal["alpha"], cal["delta"])
+        return (float(Ks), float(Kd), int(R["iters"]))
+    return evaluate
+
+
+def hip_labor_vfi_evaluator(cal, L, start, T=10000, tol=1e-5, max_iter=1000, psi=1.0, eta=2.0):
+    """The evaluator on this rank's GPU, one solve after another (host tier)."""
+    from .sim import sim_capital
+    from .vfi import labor_vfi_solve
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+
+    def solve(st, r, w):
+        return labor_vfi_solve(st["v_old"], a, s, P, L, r, w, cal["beta"], cal["sigma"], psi, eta,
+                               tol, max_iter, v_new=st["v_new"], policies=st["policies"])
+
+    def simulate(pk, z1, k1, u):
+        return sim_capital(pk, a, P, z1, k1, u)
+    return labor_vfi_evaluator(cal, solve, simulate, start, T)
+
+
+def labor_ge_batch_call(r, start, cal, L, z1, k1, blocks, psi=1.0, eta=2.0, tol=1e-5,
+                        max_iter=1000, n_devices=1):
+    """aiy_labor_ge_batch (C ABI): K_s, K_d and iteration count at every rate in `r`, each from
+    `start` (labor_start; v_new / policies None = zeros), with uniforms blocks[c] (T-1 draws) for
+    candidate c; z1 1-based."""
+    from ._capi import check, d, i64, ip, lib, ptr
+    r = np.ascontiguousarray(r, np.float64)
+    n = r.size
+    N, Na = cal["N"], cal["Na"]
+    U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
+    T = U.shape[0] + 1
+    f = lambda x: None if x is None else np.asfortranarray(x, dtype=np.float64)
+    v, vn = f(start["v_old"]), f(start.get("v_new"))
+    pol = start.get("policies") or (None, None, None, None)
+    pk, pl, pc = f(pol[0]), f(pol[1]), f(pol[2])
+    lin = None if pol[3] is None else np.asfortranarray(pol[3], dtype=np.int32)
+    for x in (v, vn, pk, pl, pc, lin):
+        if x is not None and x.shape != (N, Na):
+            raise ValueError(f"start arrays must be (N, Na) = {(N, Na)}")
+    a = np.ascontiguousarray(cal["a_grid"], np.float64)
+    s = np.ascontiguousarray(cal["s"], np.float64)
+    P = np.asfortranarray(cal["P"], dtype=np.float64)
+    L = np.ascontiguousarray(L, np.float64)
+    Ks, Kd, it = np.empty(n), np.empty(n), np.empty(n, np.int64)
+    check(lib().aiy_labor_ge_batch(ptr(r), i64(n), ptr(v), ptr(vn), ptr(pk), ptr(pl), ptr(pc),
+                                   ptr(lin), ptr(a), ptr(s), ptr(P), ptr(L), i64(N), i64(Na),
+                                   i64(L.size), d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
+                                   d(cal["sigma"]), d(psi), d(eta), d(cal["labor"]), d(tol),
+                                   i64(max_iter), i64(z1), d(k1), i64(T), ptr(U), ip(n_devices),
+                                   ptr(Ks), ptr(Kd), ptr(it)))
+    return Ks, Kd, it
+
+
+def hip_labor_batch_evaluator(cal, L, start, T=10000, tol=1e-5, max_iter=1000, n_devices=1,
+                              psi=1.0, eta=2.0):
+    """The node evaluator on the batched device path: all of a round's nodes of this rank in one
+    aiy_labor_ge_batch call (one launch per sweep over all of them, one launch of the chains per
+    GPU).  Same per-node arithmetic as hip_labor_vfi_evaluator, so the traces are identical."""
+    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
+    head, blocks = mc_stream(T)
+    z1 = int(math.ceil(N * head[0]))
+    k1 = a[int(math.ceil(Na * head[1])) - 1]
+
+    def many(nodes):
+        Ks, Kd, it = labor_ge_batch_call([n.r for n in nodes], start, cal, L, z1, k1,
+                                         [blocks[n.depth] for n in nodes], psi, eta, tol,
+                                         max_iter, n_devices)
+        return [(float(Ks[q]), float(Kd[q]), int(it[q])) for q in range(len(nodes))]
+
+    def evaluate(node):
+        return many([node])[0]
+    evaluate.many = many
+    return evaluate
+
+
+# tree levels per round on one GPU (measured: DESIGN.md §5, profiles/r10_labor_batch_ab.txt)
+LABOR_LEVELS_ONE_GPU = 2
+
+
+def aiyagari_labor_vfi_multisection(Na=400, levels=None, rank=0, world=1, allgather=None, r0=0.04,
+                                    batched=True, T=10000, tol=1e-5, max_iter=1000, psi=1.0,
+                                    eta=2.0):
+    """The GE of Aiyagari_Endogenous_Labor_VFI.m with the candidate rates of the next `levels`
+    bisection steps evaluated at once.  Every rank solves r0 from v = 0 (the script's first
+    solve), then the rounds, every candidate warm from that solution (v_old, v_new and the
+    policies: path independence, see the module docstring); batched=True runs a round's nodes of
+    this rank in one aiy_labor_ge_batch call.  levels=None: LABOR_LEVELS_ONE_GPU on one rank,
+    else auto_levels(world).  The script's chained warm start takes the same bracket decisions
+    (tests/test_labor_batch_gpu.py)."""
+    from . import calibration as cb
+    from .vfi import labor_vfi_solve
+    if levels is None:
+        levels = LABOR_LEVELS_ONE_GPU if world == 1 else auto_levels(world)
+    cal, L = labor_calibration(Na)
+    R0 = labor_vfi_solve(np.zeros((cal["N"], Na)), cal["a_grid"], cal["s"], cal["P"], L, r0,
+                         cb.wage(r0, cal["alpha"], cal["delta"]), cal["beta"], cal["sigma"], psi,
+                         eta, tol, max_iter)
+    start = labor_start(R0)
+    if batched:
+        ev = hip_labor_batch_evaluator(cal, L, start, T, tol, max_iter, 1, psi, eta)
+    else:
+        ev = hip_labor_vfi_evaluator(cal, L, start, T, tol, max_iter, psi, eta)
+    tr = multisection(ev, -0.05, 1 / cal["beta"] - 1, levels=levels, rank=rank, world=world,
+                      allgather=allgather if allgather else (torch_allgather if world > 1 else None))
+    tr.iters = [int(R0["iters"])] + tr.iters
+    return tr

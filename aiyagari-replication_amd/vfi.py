@@ -131,6 +131,17 @@ class Workspace:
         check(lib().aiy_ws_egm_batch_counts(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_labor_batch(self, min_candidates: int = 0):
+        """The batched labour solve's one-launch-per-sweep path from `min_candidates` on (0: the
+        measured default, 1: whenever the shape fits); results do not depend on it."""
+        check(lib().aiy_ws_set_labor_batch(self._h, ip(min_candidates)))
+
+    def labor_batch_counts(self):
+        """(batched solves, per-candidate fallback solves) of labor_solve_batch_dev so far."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib().aiy_ws_labor_batch_counts(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_variant(self, variant: int):
         """Screen-kernel geometry (tuning; results identical), see aiy_ws_set_variant."""
         check(lib().aiy_ws_set_variant(self._h, ip(variant)))
@@ -280,3 +291,23 @@ def _ws_labor_sweeps(self, v_a, v_b, a_grid, s, P, labor_choice, r, w, beta, sig
 
 
 Workspace.labor_vfi_sweeps = _ws_labor_sweeps
+
+
+def labor_solve_batch_dev(ws, r, w, v_a, v_b, a_grid, s, P, labor_choice, beta, sigma, psi, eta,
+                          tol, max_iter, lin, policy_k=None, policy_l=None, policy_c=None,
+                          use_hint=False, stream=None):
+    """A3 at C = len(r) rates on device (aiy_labor_vfi_solve_batch_dev): v_a (each candidate's
+    v_old), v_b (its incoming v_new), lin (0-based l + Nl*k) and the policies are [C][N][Na]
+    tensors, in/out.  Returns (iters, which) as lists: candidate c holds v_new in v_b[c] if
+    which[c] else v_a[c] (its v_old in the other)."""
+    r = np.ascontiguousarray(r, np.float64)
+    w = np.ascontiguousarray(w, np.float64)
+    n = r.size
+    it = np.zeros(n, np.int64)
+    which = np.zeros(n, np.int32)
+    check(lib().aiy_labor_vfi_solve_batch_dev(
+        ws.handle, i64(n), ptr(r), ptr(w), ptr(v_a), ptr(v_b), ptr(a_grid), ptr(s), ptr(P),
+        ptr(labor_choice), d(beta), d(sigma), d(psi), d(eta), d(tol), i64(max_iter),
+        ip(1 if use_hint else 0), ptr(lin), ptr(policy_k), ptr(policy_l), ptr(policy_c), ptr(it),
+        ptr(which), stream_handle(stream)))
+    return [int(x) for x in it], [int(x) for x in which]

@@ -155,6 +155,25 @@ int aiy_egm_ge_batch(const double* r, const double* w, int64_t C, const double* 
                      const double* uniforms, int n_devices, double* k_supply, double* k_demand,
                      int64_t* iters, int32_t* status);
 
+/* E2 — the same for Aiyagari_Endogenous_Labor_VFI.m: for each candidate c the body of one GE
+ * step (:166-245): the labour VFI at r[c] and its own w = (1-α)(α/(r+δ))^(α/(1-α)), every
+ * candidate from the same v_start, incoming v_new and policies (N x Na column-major; the script
+ * carries them across GE steps and a state with no feasible (l, a') keeps them, :85;
+ * v_new_start, policy_*_start and policy_lin_start — 1-based — are nullable: zeros / index 1),
+ * the Monte-Carlo supply on policy_k with column c of `uniforms`, and K_d from `labor`.  One
+ * batched solve (aiy_labor_vfi_solve_batch_dev) and one batched launch of the chains per device.
+ * Layouts, errors (AIY_FIND_EMPTY included) and the device split as aiy_ge_batch.  Out (C each):
+ * k_supply, k_demand, iters. */
+int aiy_labor_ge_batch(const double* r, int64_t C, const double* v_start,
+                       const double* v_new_start, const double* policy_k_start,
+                       const double* policy_l_start, const double* policy_c_start,
+                       const int32_t* policy_lin_start, const double* a_grid, const double* s,
+                       const double* P, const double* labor_choice, int64_t N, int64_t Na,
+                       int64_t Nl, double alpha, double delta, double beta, double sigma,
+                       double psi, double eta, double labor, double tol, int64_t max_iter,
+                       int64_t z1, double k1, int64_t T, const double* uniforms, int n_devices,
+                       double* k_supply, double* k_demand, int64_t* iters);
+
 /* A6 — replaces Krusell_Smith_VFI.m:149-168 (policy improvement with fminbnd).
  * value, k_opt: k x K x S column-major (S = 4); B 4; P 4 x 4; params = 13 doubles {beta, alpha,
  * delta, k_min, k_max, ug, ub, l_bar, mu, z_grid(1), z_grid(2), eps_grid(1), eps_grid(2)}.  nfev (nullable,
@@ -377,6 +396,36 @@ int aiy_labor_vfi_sweeps_dev(aiy_ws* ws, double* v_a, double* v_b, const double*
                              double eta, const int32_t* hint, int64_t nsweeps, int32_t* lin,
                              double* policy_k, double* policy_l, double* policy_c, double* diff,
                              void* stream);
+/* A3 at C candidate rates on device: candidate c's whole loop
+ * Aiyagari_Endogenous_Labor_VFI.m:64-122 at (r[c], w[c]) (host [C]; GE copy :166-219), its own
+ * stop at :115-118.  v_a (in: each candidate's starting v_old), v_b (in: each candidate's
+ * incoming v_new, which a state with no feasible (l, a') keeps, :85), lin (0-based l + Nl·k, as
+ * the sweep entry points; in: the incoming index, and sweep 1's hint when use_hint != 0),
+ * policy_k, policy_l, policy_c (in/out, nullable): device [C][N][Na]; labor_choice: device [Nl],
+ * Nl the workspace's.  Out (host [C]): iters, which = 1 if the candidate's v_new is in v_b (its
+ * v_old in v_a), else 0.  Where the shape takes the small-grid one-launch sweep (integer sigma in
+ * [2, 9], Na within aiy_ws_set_wide's bound, Nl <= 16, N < 32) and C is at least the workspace's
+ * threshold (aiy_ws_set_labor_batch), every sweep is ONE launch over all candidates still
+ * running, each candidate tested and frozen on the device, and the host reads the stop flags
+ * once per aiy_ws_set_speculation sweeps; otherwise the candidates run one after another through
+ * the single-rate solve.  Either way the outputs equal C separate solves (aiy_labor_vfi_solve)
+ * bit for bit.  The call synchronises the stream.  Errors before any device work: NULL
+ * arguments, C outside [1, 2^20], max_iter < 1 (AIY_BAD_ARG / AIY_BAD_SHAPE), non-finite r or w
+ * (AIY_NON_FINITE), C·Nl·N·Na past int32 (AIY_BAD_SHAPE). */
+int aiy_labor_vfi_solve_batch_dev(aiy_ws* ws, int64_t C, const double* r, const double* w,
+                                  double* v_a, double* v_b, const double* a_grid,
+                                  const double* s, const double* P, const double* labor_choice,
+                                  double beta, double sigma, double psi, double eta, double tol,
+                                  int64_t max_iter, int use_hint, int32_t* lin, double* policy_k,
+                                  double* policy_l, double* policy_c, int64_t* iters,
+                                  int32_t* which, void* stream);
+/* the batched labour solve's dispatch on this workspace: the one-launch-per-sweep path from
+ * min_candidates on (0, the default: the measured threshold, DESIGN.md §5 — never a single
+ * candidate; 1: whenever the shape fits).  Results do not depend on it. */
+int aiy_ws_set_labor_batch(aiy_ws* ws, int min_candidates);
+/* how often aiy_labor_vfi_solve_batch_dev took each path on this workspace since it was created:
+ * batched solves (calls), and per-candidate solves of the other path (both nullable). */
+int aiy_ws_labor_batch_counts(aiy_ws* ws, int64_t* batched_solves, int64_t* fallback_solves);
 int aiy_egm_step_dev(aiy_ws* ws, const double* policy_c, const double* a_grid,
                      const double* s, const double* P, double r, double w, double beta,
                      double sigma, double amin, int labor, double phi, double theta,
