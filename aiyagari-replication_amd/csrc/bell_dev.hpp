@@ -139,6 +139,40 @@ __device__ __forceinline__ double wave_fmax_d(double x) {
     return readlane_d(x, 63);
 }
 
+// Lanes per group of the tree kernel's 8-block test ("group-level bound"): the
+// 64 sub-block bounds of a superblock are tested in place, one per lane, against the lowest
+// bar and the largest cash on hand of each group of eight consecutive lanes, and every bit of
+// the groups' union is then confirmed per lane.
+constexpr int kTreeGroup = 8;
+
+// min / max of x over each group of kTreeGroup consecutive lanes, left in every lane of the
+// group: the first three steps of the wave ladder above (lane ^ 1, lane ^ 2, mirror of 8 —
+// each step hands a lane the other half of its group).  NaN drops out as above.
+__device__ __forceinline__ double group_fmin_d(double x) {
+    x = fmin(x, dpp_d<0xB1>(x));
+    x = fmin(x, dpp_d<0x4E>(x));
+    return fmin(x, dpp_d<0x141>(x));
+}
+__device__ __forceinline__ double group_fmax_d(double x) {
+    x = fmax(x, dpp_d<0xB1>(x));
+    x = fmax(x, dpp_d<0x4E>(x));
+    return fmax(x, dpp_d<0x141>(x));
+}
+// the rest of the wave ladder from a value that already holds its group's min / max in every
+// lane: wave_fmin_d(x) == wave_rest_fmin_d(group_fmin_d(x)), the same operations
+__device__ __forceinline__ double wave_rest_fmin_d(double x) {
+    x = fmin(x, dpp_d<0x140>(x));
+    x = fmin(x, dpp_d<0x142, 0xa>(x));
+    x = fmin(x, dpp_d<0x143, 0xc>(x));
+    return readlane_d(x, 63);
+}
+__device__ __forceinline__ double wave_rest_fmax_d(double x) {
+    x = fmax(x, dpp_d<0x140>(x));
+    x = fmax(x, dpp_d<0x142, 0xa>(x));
+    x = fmax(x, dpp_d<0x143, 0xc>(x));
+    return readlane_d(x, 63);
+}
+
 // Wave-level block bound: (dmax, a0) is one block's bound in this lane, bmin the minimum of the
 // wave's bars and cmax the maximum of its cash on hand (both wave-uniform).  True whenever some
 // sub-state of some lane passes the per-lane bound (dmax − B)·max(coh − a0, 0)^NP ≥ kThr: the

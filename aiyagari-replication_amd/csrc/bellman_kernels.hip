@@ -709,7 +709,10 @@ __global__ __launch_bounds__(256, MINW) void bell_screen_kernel(BellArgs A, int 
 //            superblock per lane in a single round trip and tested there, once for the whole
 //            wave, against its lowest bar and its largest cash on hand (screen_wave)
 //   level 1/2: inside a passing superblock, one round trip fetches its 64 sub-block maxima
-//            (Dmax8) and sub-block starts; 64-blocks are their 8-lane butterfly maxima
+//            (Dmax8) and sub-block starts, one per lane.  A1: tested there against the lowest
+//            bar and the largest cash of each group of 8 lanes (the compare is the 64-bit mask),
+//            then every set bit confirmed per lane.  Labour: 64-blocks (the 8-lane butterfly
+//            maxima), then the 8-blocks of every passing one, per lane, eight bounds a call
 //   level 3: the candidates of every passing 64-block are staged in LDS together (one round
 //            trip); each candidate of a passing sub-block gets the exact fp64 screen test, and
 //            the candidates that pass get their exact value in the literal MATLAB order
@@ -962,7 +965,8 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     // extrapolated window, climb) and the screen's (VERDICT r4 "do this" 1)
     // nsup: superblocks entered; nwv: wave-level tests of the level-0 bounds (64 lane
     // evaluations each, whatever the number of sub-states)
-    unsigned nhits = nsu, nsup = 0, nwv = 0, nblk = 0, nfine = 0, lane_pairs = 0;
+    // ngt: group-level tests of the 8-block bounds (64 lane evaluations each, like nwv)
+    unsigned nhits = nsu, nsup = 0, nwv = 0, nblk = 0, ngt = 0, nfine = 0, lane_pairs = 0;
     const long long t_start = (INS && A.trace) ? (long long)wall_clock64() : 0;
     // phase cycle counters (trace mode): startup, superblock() calls, fine screens, exact paths
     long long cyc[4] = {0, 0, 0, 0}, c_mark = (INS && A.trace) ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -1028,6 +1032,31 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                                                       : __builtin_nan("");
         };
         set_B();
+        // Group bars (GRP): for each group of GL consecutive lanes the minimum of its valid
+        // sub-states' bars (NaN bars drop out; idx < 0 gives −inf) and the maximum of their
+        // cash on hand (invalid sub-states: −inf), kept in every lane of the group and fetched
+        // with v_readlane just before its test.  Taken here for the first superblock and once
+        // more after it; the exact paths only raise the lanes' bars, so the older minimum stays
+        // a valid (only looser) bar.
+        // Labour keeps the per-lane cascade (!GRP): a lane's five sub-states differ in cash
+        // by the whole labour grid, so one (lowest bar, largest cash) pair per group is far too
+        // loose there.
+        constexpr bool GRP = !LAB;
+        constexpr int GL = kTreeGroup;
+        double gB = __builtin_nan(""), gC = -__builtin_inf();
+        auto set_G = [&]() __attribute__((always_inline)) {
+            double bl = __builtin_nan(""), cl = -__builtin_inf();
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int q = 0; q < LB; ++q) {
+                    bl = fmin(bl, B[r][q]);
+                    cl = fmax(cl, (okr[r] && l0 + q < Nl) ? coh[r][q] : -__builtin_inf());
+                }
+            gB = group_fmin_d(bl);
+            gC = group_fmax_d(cl);
+        };
+        if constexpr (GRP) set_G();
 
         // eight block bounds at once (independent dependency chains, so their latencies
         // overlap): lanes l0 + stride*u of (dv, av) hold (Dmax, a at the block start); bit u
@@ -1165,8 +1194,43 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             dm8 = oku ? A.Dm8[(size_t)i * A.nb8 + sub] : -__builtin_inf();
             a8 = oku ? a[sub << 3] : 0.0;
         };
+        // the candidates of every 64-block with a passing 8-block: loads issued together
+        auto stage = [&](int sbase, unsigned long long pass, double2 (&st)[8])
+                         __attribute__((always_inline)) {
+            if constexpr (LEAN) {
+                // no register set for all eight: the passing 64-blocks two at a time, both
+                // loads issued before either LDS write (a load and its write in one guarded
+                // block would cost one L2 round trip per block)
+                unsigned bm = 0;
+#pragma unroll
+                for (int b = 0; b < 8; ++b) bm |= ((pass >> (8 * b)) & 0xffull) ? 1u << b : 0u;
+                while (bm) {
+                    const int b0 = __builtin_ctz(bm);
+                    bm &= bm - 1;
+                    const int b1 = bm ? __builtin_ctz(bm) : -1;
+                    if (bm) bm &= bm - 1;
+                    const int k0 = min(sbase + (b0 << 6) + lane, Na - 1);
+                    const double2 v0 = make_double2(a[k0], Drow[k0]);
+                    double2 v1 = make_double2(0.0, 0.0);
+                    if (b1 >= 0) {
+                        const int k1 = min(sbase + (b1 << 6) + lane, Na - 1);
+                        v1 = make_double2(a[k1], Drow[k1]);
+                    }
+                    s_cand[lw][(b0 << 6) + lane] = v0;
+                    if (b1 >= 0) s_cand[lw][(b1 << 6) + lane] = v1;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 8; ++b)  // all loads issued before any is used
+                    if ((pass >> (8 * b)) & 0xffull) {
+                        const int k = min(sbase + (b << 6) + lane, Na - 1);
+                        st[b] = make_double2(a[k], Drow[k]);
+                    }
+            }
+        };
         // one superblock, blocks b with b % bstep == bsel, in two halves.  prep: the bound tests
-        // of its 64-blocks and 8-blocks (v_readlane of the sub-block bounds, no memory) and the
+        // of its 8-blocks (group-level in place, then confirmed; labour: the per-lane cascade
+        // over 64-blocks and 8-blocks — v_readlane of the sub-block bounds, no memory) and the
         // loads of the candidates of every passing 64-block into registers.  finish: those
         // registers to LDS, then the fine screen of every passing 8-block.  The main loop runs
         // prep of superblock n+1 before finish of superblock n, so the candidate loads of n+1
@@ -1177,6 +1241,71 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                         __attribute__((always_inline)) -> unsigned long long {
             stamp(0);
             const int sbase = sb << 9;  // first candidate of the superblock
+            if constexpr (GRP) {
+                // Group-level test: lane u holds the bound of 8-block u; against group g's bar
+                // and cash the compare's result is already the mask of the 8-blocks that some
+                // sub-state of the group may pass (screen_wave's argument on GL lanes).  The
+                // groups' chains are independent and staged together; their union, cut to the
+                // feasible range and to this wave's share, is the pass mask.
+                // (the lean register budget stages four chains at a time, as its screens do)
+                constexpr int NG = 64 / GL, CH = LEAN ? 4 : 8;
+                static_assert(NG % CH == 0, "whole chunks of groups");
+                unsigned long long any = 0;
+#pragma unroll
+                for (int g0 = 0; g0 < NG; g0 += CH) {
+                    double cx[CH], dd[CH], t[CH];
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) {
+                        cx[u] = readlane_d(gC, (g0 + u) * GL) - a8;
+                        dd[u] = dm8 - readlane_d(gB, (g0 + u) * GL);
+                    }
+                    AIY_SCHED_BARRIER();
+                    screen_t<NP, CH>(t, cx, dd);
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) any |= __ballot(t[u] >= kThr);
+                }
+                if (INS && (A.hitcount || A.trace)) ngt += NG;
+                // 8-blocks inside the feasible range (sbase < kg: at least one)
+                const int nfe = min(64, (kg - sbase + 7) >> 3);
+                unsigned long long pass = any & (nfe >= 64 ? ~0ull : (1ull << nfe) - 1ull);
+                // this wave's share: with subsplit the 8-blocks bsel, bsel + bstep, ... (every
+                // wave computes the same mask, so no exchange); without, its own 64-blocks
+                if (bstep > 1) {
+                    const unsigned long long one = subsplit ? 0x01ull : 0xffull;
+                    unsigned long long pat = one << (subsplit ? bsel : 8 * bsel);
+                    for (int sh = subsplit ? bstep : 8 * bstep; sh < 64; sh <<= 1) pat |= pat << sh;
+                    pass &= pat;
+                }
+                // Confirmation: every 8-block of the group mask gets the per-lane test (its bound
+                // broadcast with v_readlane, every sub-state against its own bar and cash, one
+                // vote) — the wave's exact union, at one test per candidate block instead of
+                // one per block of every passing 64-block.
+                if (INS && (A.hitcount || A.trace)) nblk += __builtin_popcountll(pass);
+                unsigned long long keep = 0;
+                for (unsigned long long m = pass; m; m &= m - 1) {
+                    const int u = __builtin_ctzll(m);
+                    const double dv = readlane_d(dm8, u), av = readlane_d(a8, u);
+                    double cx[RL], dd[RL], t[RL];
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int q = 0; q < LB; ++q) {
+                            cx[r * LB + q] = coh[r][q] - av;
+                            dd[r * LB + q] = dv - B[r][q];
+                        }
+                    screen_t<NP, RL>(t, cx, dd);
+                    bool p = false;
+#pragma unroll
+                    for (int m2 = 0; m2 < RL; ++m2) p = p || t[m2] >= kThr;
+                    if (__any(p)) keep |= 1ull << u;
+                }
+                pass = keep;
+                if (INS && A.trace && lane == 0) lane_pairs += __builtin_popcountll(pass);
+                stage(sbase, pass, st);
+                stamp(1);
+                return pass;
+            }
+            // !GRP, the per-lane cascade.
             // 64-block maxima at lanes 8b (the only lanes read): lane ^ 1, lane ^ 2, lane + 4
             double dm64 = dm8;
             dm64 = fmax(dm64, dpp_d<0xB1>(dm64));
@@ -1215,36 +1344,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     pass = all & (pat << bsel);
                 }
             }
-            if constexpr (LEAN) {
-                // no register set for all eight: the passing 64-blocks two at a time, both
-                // loads issued before either LDS write (a load and its write in one guarded
-                // block would cost one L2 round trip per block)
-                unsigned bm = 0;
-#pragma unroll
-                for (int b = 0; b < 8; ++b) bm |= ((pass >> (8 * b)) & 0xffull) ? 1u << b : 0u;
-                while (bm) {
-                    const int b0 = __builtin_ctz(bm);
-                    bm &= bm - 1;
-                    const int b1 = bm ? __builtin_ctz(bm) : -1;
-                    if (bm) bm &= bm - 1;
-                    const int k0 = min(sbase + (b0 << 6) + lane, Na - 1);
-                    const double2 v0 = make_double2(a[k0], Drow[k0]);
-                    double2 v1 = make_double2(0.0, 0.0);
-                    if (b1 >= 0) {
-                        const int k1 = min(sbase + (b1 << 6) + lane, Na - 1);
-                        v1 = make_double2(a[k1], Drow[k1]);
-                    }
-                    s_cand[lw][(b0 << 6) + lane] = v0;
-                    if (b1 >= 0) s_cand[lw][(b1 << 6) + lane] = v1;
-                }
-            } else {
-#pragma unroll
-                for (int b = 0; b < 8; ++b)  // all loads issued before any is used
-                    if ((pass >> (8 * b)) & 0xffull) {
-                        const int k = min(sbase + (b << 6) + lane, Na - 1);
-                        st[b] = make_double2(a[k], Drow[k]);
-                    }
-            }
+            stage(sbase, pass, st);
             stamp(1);
             return pass;
         };
@@ -1329,16 +1429,24 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         // valid (only looser) bar.
         double bmin, cmax;
         {
-            double bl = __builtin_nan(""), cl = -__builtin_inf();
+            // (group bars: refreshed when the first superblock may have raised the bars; the
+            // wave's pair is the rest of the same reduction ladder)
+            if constexpr (GRP) {
+                if (sfirst >= 0) set_G();
+                bmin = wave_rest_fmin_d(gB);
+                cmax = wave_rest_fmax_d(gC);
+            } else {
+                double bl = __builtin_nan(""), cl = -__builtin_inf();
 #pragma unroll
-            for (int r = 0; r < R; ++r)
+                for (int r = 0; r < R; ++r)
 #pragma unroll
-                for (int q = 0; q < LB; ++q) {
-                    bl = fmin(bl, B[r][q]);
-                    cl = fmax(cl, (okr[r] && l0 + q < Nl) ? coh[r][q] : -__builtin_inf());
-                }
-            bmin = wave_fmin_d(bl);
-            cmax = wave_fmax_d(cl);
+                    for (int q = 0; q < LB; ++q) {
+                        bl = fmin(bl, B[r][q]);
+                        cl = fmax(cl, (okr[r] && l0 + q < Nl) ? coh[r][q] : -__builtin_inf());
+                    }
+                bmin = wave_fmin_d(bl);
+                cmax = wave_fmax_d(cl);
+            }
         }
         // the passing superblocks in order: one wave-level test of the 64 level-0 bounds a
         // group (screen_wave: lane u holds superblock g + u), balloted into a mask of this
@@ -1441,7 +1549,11 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     if (INS && A.trace) {  // instrumentation (aiy_ws_set_timing bit 2): per-wave sums into wave 0
         __shared__ unsigned s_cnt[W][4];
         __shared__ unsigned s_pairs;
-        unsigned pairs = lane_pairs, sums[4] = {nsup, nblk, nfine, nhits};
+        // block tests in one unit, 64·R·LB lane evaluations (a cascade bound or a confirmation):
+        // a group test is 64, and ngt a multiple of 8 with R·LB <= 2 where groups are tested
+        static_assert(LAB || 8 % (R * LB) == 0, "group tests in whole block-test units");
+        const unsigned nblk_all = nblk + ngt / (R * LB);
+        unsigned pairs = lane_pairs, sums[4] = {nsup, nblk_all, nfine, nhits};
         if constexpr (W == 1) {  // one wave: a shuffle sum, no barrier (packed workgroups)
             for (int o = 32; o > 0; o >>= 1) pairs += __shfl_xor(pairs, o);
         } else {
@@ -1449,7 +1561,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             __syncthreads();
             atomicAdd(&s_pairs, lane_pairs);
             if (lane == 0) {
-                s_cnt[wave][0] = nsup; s_cnt[wave][1] = nblk; s_cnt[wave][2] = nfine; s_cnt[wave][3] = nhits;
+                s_cnt[wave][0] = nsup; s_cnt[wave][1] = nblk_all; s_cnt[wave][2] = nfine; s_cnt[wave][3] = nhits;
             }
             __syncthreads();
             pairs = s_pairs;
@@ -1473,7 +1585,9 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             tr[12] = t_boot;                                   // kernel entry (wall clock)
             tr[13] = c_mark0 - c_boot;                         // start-up cycles (hint, climb)
             tr[14] = (long long)__builtin_amdgcn_s_memtime() - c_end;  // output cycles
-            tr[15] = pairs;  // (state, sub-block) pairs passing the 8-block bound
+            // labour (cascade): (state, sub-block) pairs passing the 8-block bound; A1 (group
+            // test): the confirmed masks' population count, i.e. 8-blocks fine-screened
+            tr[15] = pairs;
         }
     }
     if (INS && A.hitcount) {  // instrumentation (aiy_ws_set_timing bit 1)
@@ -1482,7 +1596,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         if (lane == 0) {
             const unsigned long long ns = 64ull * R * LB;
             atomicAdd(hc + 1, nwv * 64ull);
-            atomicAdd(hc + 2, nblk * ns);
+            atomicAdd(hc + 2, nblk * ns + ngt * 64ull);
             if (nfine) atomicAdd(hc + 3, nfine * ns);
         }
     }

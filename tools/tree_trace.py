@@ -58,11 +58,17 @@ def main():
                 print("  entry->start us p50/p90/max: %s; start-up cycles mean %.0f; output cycles "
                       "mean %.0f; entry spread %.1f us" % (np.percentile(boot, [50, 90, 100]).round(1),
                       T[:, 13].mean(), T[:, 14].mean(), (T[:, 12].max() - T[:, 12].min()) / 100.0))
+                # record field 15: with the per-lane cascade (labour) the (state, sub-block) pairs
+                # passing the 8-block bound, summed over lanes; with the group-level test (A1)
+                # the population count of the confirmed pass masks, i.e. the item's fine-screened
+                # 8-blocks (field 4, block tests, then counts confirmations and group tests, all in
+                # units of 64·R·LB lane evaluations: eight group tests are 8 / R units)
                 pairs = T[:, 15].astype(float)
                 nsubpass = T[:, 5].astype(float) / 8.0  # candidate tests / 8 per passing sub-block
-                print("  (state, sub-block) pairs passing per wave: mean %.1f; passing sub-blocks "
-                      "x 64 lanes: mean %.1f (ratio %.3f)" % (pairs.mean(), (nsubpass * 64).mean(),
-                      pairs.sum() / max((nsubpass * 64).sum(), 1)))
+                print("  field 15 (pairs, or confirmed 8-blocks with the group test) per item: mean "
+                      "%.1f; passing sub-blocks x 64 lanes: mean %.1f (ratio %.3f)"
+                      % (pairs.mean(), (nsubpass * 64).mean(),
+                         pairs.sum() / max((nsubpass * 64).sum(), 1)))
                 cy = T[:, 8:12].astype(float)
                 print("  wave-0 cycles mean: top/sup-tests %.0f  block-tests %.0f  fine %.0f  exact %.0f"
                       % tuple(cy.mean(0)))
