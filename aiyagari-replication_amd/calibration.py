@@ -116,6 +116,15 @@ def krusell_smith(k_size=100, K_size=4, K_min=30.0, K_max=50.0, beta=0.99, k_min
     x = linspace01(k_size)
     k_grid = (x ** 7) * (k_max - k_min) + k_min
     k_grid[0], k_grid[-1] = k_min, k_max
+    # From k_size = 2,043 on (the scaling grids; the script runs 100) x^7·(k_max − k_min) falls
+    # below half an ulp of k_min for the first points, which then repeat k_min.  MATLAB's
+    # interpolants refuse a repeated grid point and so does every KS entry point
+    # (check_grid_strict), so a repeat moves to the next double: strictly increasing, and
+    # unchanged wherever the formula already is (every k_size up to 2,042 in particular).
+    if (np.diff(k_grid) <= 0).any():
+        for i in range(1, k_size - 1):
+            if k_grid[i] <= k_grid[i - 1]:
+                k_grid[i] = np.nextafter(k_grid[i - 1], np.inf)
     K_grid = K_min + (K_max - K_min) * linspace01(K_size)
     pgg = pbb = 1 - 1 / 8
     pgb, pbg = 1 - pgg, 1 - pbb

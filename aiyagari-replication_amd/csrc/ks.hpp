@@ -72,6 +72,8 @@ struct KsParams {  // the 13-double parameter block, in order
 };
 void ks_slices(const KsParams& p, const double* B, const double* K_grid, int nK,
                std::vector<KsSlice>& out);
+// AIY_NON_FINITE if value holds ±inf (the host-tier VFI entry points; NaN is accepted)
+int ks_check_value(const double* value, size_t n);
 struct KsOut {
     int iters;
     double rel;

@@ -107,7 +107,7 @@ int ks_dev_create_slice(const double* k_grid, const double* K_grid, const double
         return fail(AIY_BAD_SHAPE, "need k_size >= 3, K_size >= 1");
     if (K0 < 0 || K1 > nK || K0 >= K1) return fail(AIY_BAD_ARG, "shard [K0, K1) must be inside [0, K_size)");
     if (s0 < 0 || s1 > 4 || s0 >= s1) return fail(AIY_BAD_ARG, "shard [s0, s1) must be inside [0, 4)");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(AIY_NO_DEVICE, "no HIP device visible");
     KsParams p;

@@ -80,7 +80,7 @@ int ks_egm_solve(double* k_opt, const double* k_grid, const double* K_grid, cons
     if (max_iter < 1 || max_iter > 2147483647) return fail(AIY_BAD_ARG, "max_iter in [1, 2^31)");
     if (!ks_egm_fits((int)nk, (int)nK))
         return fail(AIY_BAD_SHAPE, "k_size x K_size too large for the one-workgroup EGM solve");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
     for (int64_t q = 0; q < nK; ++q)
         if (!(K_grid[q] > 0) || !std::isfinite(K_grid[q]))
             return fail(AIY_NON_FINITE, "K_grid must be positive and finite");
@@ -143,7 +143,7 @@ int ks_egm_solve_jacobi(double* k_opt, const double* k_grid, const double* K_gri
     if (ks_egm_jacobi_lds_bytes((int)nk) > 150 * 1024)
         return fail(AIY_BAD_SHAPE, "k_size too large for one workgroup per (s, K) pair");
     if (max_iter < 1 || max_iter > 2147483647) return fail(AIY_BAD_ARG, "max_iter in [1, 2^31)");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
     for (int64_t q = 0; q < nK; ++q)
         if (!(K_grid[q] > 0) || !std::isfinite(K_grid[q]))
             return fail(AIY_NON_FINITE, "K_grid must be positive and finite");

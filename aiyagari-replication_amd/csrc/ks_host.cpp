@@ -54,6 +54,17 @@ void ks_slices(const KsParams& p, const double* B, const double* K_grid, int nK,
         }
 }
 
+// The host-tier VFI entry points refuse ±inf in value (NaN passes, as in the script): the
+// tabled-reciprocal division of the pchip kernels (div_by_rcp) is the IEEE quotient for finite
+// and NaN numerators only — an infinite value difference comes out NaN where a / b keeps ±inf.
+int ks_check_value(const double* value, size_t n) {
+    for (size_t q = 0; q < n; ++q)
+        if (std::isinf(value[q]))
+            return fail(AIY_NON_FINITE, "value(%lld) is infinite (finite or NaN entries only)",
+                        (long long)q + 1);
+    return AIY_OK;
+}
+
 struct KsDev {
     double *kg, *kgt, *P, *V, *V2, *dV, *dV2, *Vold, *kopt;
     int* nfev;
@@ -69,7 +80,8 @@ static int ks_stage(HostCtx* c, const double* value, const double* k_opt, const 
     if (!value || !k_grid || !K_grid || !B || !P || !params)
         return fail(AIY_BAD_ARG, "NULL argument");
     if (nk < 3 || nK < 1) return fail(AIY_BAD_SHAPE, "need k_size >= 3 and K_size >= 1");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
+    AIY_TRY(ks_check_value(value, (size_t)nk * nK * 4));
     KsParams p;
     memcpy(&p, params, sizeof p);
     std::vector<KsSlice> sl;

@@ -122,7 +122,7 @@ int ks_vfi_solve_direct_impl(double* value, double* k_opt, const double* k_grid,
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(AIY_NO_DEVICE, "no HIP device visible");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
     const int W = (int)std::max<int64_t>(1, std::min<int64_t>(n_shards, 2 * nK));
     KsParams p;
     memcpy(&p, params, sizeof p);
@@ -334,7 +334,7 @@ int ks_vfi_solve_sharded_impl(double* value, double* k_opt, const double* k_grid
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(AIY_NO_DEVICE, "no HIP device visible");
-    AIY_TRY(check_grid(k_grid, nk));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
     const int W = (int)std::max<int64_t>(1, std::min<int64_t>(n_shards, 2 * nK));
     const int m = std::max(1, depth);
     KsParams p;
@@ -558,6 +558,7 @@ extern "C" int ks_vfi_solve_sharded(double* value, double* k_opt, const double* 
     if (max_vfi < 1 || howard_steps < 0) return fail(AIY_BAD_ARG, "max_vfi >= 1, howard_steps >= 0");
     if (nk < 3 || nK < 1) return fail(AIY_BAD_SHAPE, "need k_size >= 3 and K_size >= 1");
     if (n_shards < 1 || depth < 0) return fail(AIY_BAD_ARG, "n_shards >= 1 and depth >= 0");
+    AIY_TRY(ks_check_value(value, (size_t)nk * nK * 4));
     std::lock_guard<std::mutex> lk(host_mutex());
     int cur = 0;
     (void)hipGetDevice(&cur);

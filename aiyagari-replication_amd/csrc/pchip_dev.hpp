@@ -10,10 +10,16 @@ __device__ __forceinline__ int sgn_dev(double x) { return (x > 0) - (x < 0); }
 
 // RN(a / b) for b > 0 from rb = RN(1 / b): q = RN(a·rb), then two residual corrections
 // q += fma(−q, b, a)·rb (Markstein: with rb correctly rounded and q faithful, the corrected
-// quotient is the correctly rounded one — no overflow or underflow here: grid spans and value
-// differences; tools/micro/fastdiv_check.c: 2·10⁸ random and adversarial pairs, one correction
-// misses 1, two miss 0).  A zero numerator keeps its sign, as IEEE a / b does for b > 0.  Five
-// dependent fp64 operations instead of the eleven of the IEEE division sequence.
+// quotient is the correctly rounded one; tools/micro/fastdiv_check.c: 2·10⁸ random and
+// adversarial pairs, one correction misses 1, two miss 0).  A zero numerator keeps its sign, as
+// IEEE a / b does for b > 0.  Five dependent fp64 operations instead of the eleven of the IEEE
+// division sequence.
+// Domain (the callers' precondition, tests/test_ks_adversarial_gpu.py): b > 0 finite — a
+// strictly increasing grid, which every KS entry point checks; b = 0 would give 0 where 0 / 0
+// is NaN — and a finite or NaN.  a = ±inf comes out NaN (fma(∓inf, b, ±inf)) where a / b keeps
+// ±inf: the host-tier entry points refuse an infinite value, the device tier (ks_dev_*) states
+// it.  Quotients or residuals that overflow or underflow (values scaled near 1e300: c3 of
+// pchip_at overflows) are not the IEEE results either; no model's values come near that.
 __device__ __forceinline__ double div_by_rcp(double a, double b, double rb) {
     double q = a * rb;
     double e = __builtin_fma(-q, b, a);

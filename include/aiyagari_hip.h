@@ -177,7 +177,9 @@ int aiy_labor_ge_batch(const double* r, int64_t C, const double* v_start,
 /* A6 — replaces Krusell_Smith_VFI.m:149-168 (policy improvement with fminbnd).
  * value, k_opt: k x K x S column-major (S = 4); B 4; P 4 x 4; params = 13 doubles {beta, alpha,
  * delta, k_min, k_max, ug, ub, l_bar, mu, z_grid(1), z_grid(2), eps_grid(1), eps_grid(2)}.  nfev (nullable,
- * k x K x S) = fminbnd function evaluations per node. */
+ * k x K x S) = fminbnd function evaluations per node.
+ * The A6/A7/A8 entry points need a strictly increasing k_grid (a repeated point:
+ * AIY_BAD_ARG); the A6/A7 ones refuse ±inf in value (AIY_NON_FINITE; NaN is accepted). */
 int ks_policy_improve(const double* value, const double* k_grid, const double* K_grid,
                       const double* B, const double* P, const double* params, int64_t nk,
                       int64_t nK, double* k_opt, int32_t* nfev);
@@ -491,7 +493,11 @@ int aiy_dist_stationary_dev(aiy_ws* ws, const double* lambda, const int32_t* pol
  * arrays (the layout of Krusell_Smith_VFI.m's `value`).  Each call writes only the shard's
  * nodes; the caller exchanges the owned value slices between ranks (an RCCL all-gather,
  * aiyagari-replication_amd/ks_dist.py) after every Howard sweep.  Same kernels as
- * ks_vfi_solve, so any sharding gives the single-device result bit for bit. */
+ * ks_vfi_solve, so any sharding gives the single-device result bit for bit.
+ * k_grid must be strictly increasing (a repeated point: AIY_BAD_ARG, as MATLAB's interpolants
+ * refuse it).  Precondition on the device arrays, which no call reads back to check: every
+ * entry of V is finite or NaN.  An infinite entry makes the slopes next to it NaN where the
+ * script keeps ±inf (the host-tier entry points return AIY_NON_FINITE for such a value). */
 typedef struct ks_dev ks_dev;
 int ks_dev_create(const double* k_grid, const double* K_grid, const double* B, const double* P,
                   const double* params, int64_t nk, int64_t nK, int64_t K0, int64_t K1,

@@ -64,6 +64,13 @@ def test_bad_inputs(pkg, gpu, golden):
         pkg.ks_egm_solve(g["k_opt0"], g["k_grid"][::-1].copy(), g["K_grid"], g["B"], g["P"], prm)
     with pytest.raises(pkg.AiyError):
         pkg.ks_egm_solve(g["k_opt0"], g["k_grid"], -g["K_grid"], g["B"], g["P"], prm)
+    # a repeated grid point (griddedInterpolant raises): AIY_BAD_ARG, both variants
+    kg = g["k_grid"].copy()
+    kg[50] = kg[49]
+    for jacobi in (False, True):
+        with pytest.raises(pkg.AiyError) as e:
+            pkg.ks_egm_solve(g["k_opt0"], kg, g["K_grid"], g["B"], g["P"], prm, jacobi=jacobi)
+        assert e.value.status == "AIY_BAD_ARG"
 
 
 @pytest.mark.parametrize("B,nK,nk,max_iter", [(None, 4, 100, 10000),
