@@ -103,6 +103,42 @@ struct EgmBatchBlocksT {
 };
 using EgmBatchBlocks = EgmBatchBlocksT<DevMem, PinnedMem>;
 
+// batched histogram solve (aiy_dist_stationary_batch_dev): the candidates' plans (keys, run
+// offsets, lottery weights), flags, results and partial sums of K on the device and the pinned
+// copies of what the host reads, sized for the largest C seen at the workspace's (N, Na)
+template <class DM, class PM>
+struct DistBatchBlocksT {
+    Buf<int, DM> key;          // device [C][N][Na]
+    Buf<int, DM> off;          // device [C][N][Na+1]
+    Buf<double, DM> wr;        // device [C][N][Na]
+    Buf<double, DM> part;      // device [C][256]
+    Buf<unsigned, DM> flags;   // device [C]
+    Buf<long long, DM> iters;  // device [C]
+    Buf<double, DM> dist;      // device [C]
+    Buf<unsigned, PM> hflags;  // pinned [C]
+    Buf<long long, PM> hiters;
+    Buf<double, PM> hdist;
+    // room for C candidates of n = N·Na states and nw = N·(Na+1) offsets; on failure the status
+    // of the first allocation that failed (what was allocated before it stays owned and is
+    // reused or freed as usual)
+    int ensure(size_t C, size_t n, size_t nw) {
+        if (nw < n || (nw && C > SIZE_MAX / nw) || C > SIZE_MAX / 256)
+            return fail(AIY_NO_MEMORY, "%zu candidates of %zu states", C, n);
+        int rc = key.ensure(C * n);
+        if (rc == AIY_OK) rc = off.ensure(C * nw);
+        if (rc == AIY_OK) rc = wr.ensure(C * n);
+        if (rc == AIY_OK) rc = part.ensure(C * 256);
+        if (rc == AIY_OK) rc = flags.ensure(C);
+        if (rc == AIY_OK) rc = iters.ensure(C);
+        if (rc == AIY_OK) rc = dist.ensure(C);
+        if (rc == AIY_OK) rc = hflags.ensure(C);
+        if (rc == AIY_OK) rc = hiters.ensure(C);
+        if (rc == AIY_OK) rc = hdist.ensure(C);
+        return rc;
+    }
+};
+using DistBatchBlocks = DistBatchBlocksT<DevMem, PinnedMem>;
+
 // events created together and destroyed with their owner
 class Events {
     std::vector<hipEvent_t> ev_;

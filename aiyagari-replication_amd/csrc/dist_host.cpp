@@ -1,6 +1,7 @@
 // A10 entry points: aiy_dist_update_dev (one histogram push on device),
-// aiy_dist_stationary_dev (iterate to the fixed point on device) and aiy_dist_stationary
-// (MATLAB layouts, K = Σ λ·a).
+// aiy_dist_stationary_dev (iterate to the fixed point on device), aiy_dist_stationary
+// (MATLAB layouts, K = Σ λ·a) and their forms for C candidate policies at once
+// (aiy_dist_stationary_batch_dev, aiy_dist_stationary_batch).
 //
 // The policy is fixed across the fixed-point iteration, so its plan (keys, lottery weights,
 // run offsets, the monotonicity flag) is built ONCE per call and read back once; every push is
@@ -185,6 +186,84 @@ int dist_stationary_dev(aiy_ws* ws, const double* lam0, const int* idx, const do
     return AIY_OK;
 }
 
+// The fixed points of C candidates (aiy_dist_stationary_batch_dev).  Batched path: one prepare
+// launch pair builds all plans, the C flag words are read once (an out-of-range index fails the
+// call before any solve), one launch solves every monotone candidate — a workgroup each, the
+// loop in LDS — followed by the batched K, and one synchronisation reads iters and dist.
+// Non-monotone candidates, and all of them when the shape does not fit or C is below the
+// workspace's threshold, run dist_stationary_dev one after another: the same additions.
+int dist_stationary_batch_dev(aiy_ws* ws, int64_t C, const double* lam0, const int* idx,
+                              const double* kp, const double* a, const double* P, double tol,
+                              int64_t max_iter, double* lam_out, double* k_dev, int64_t* iters,
+                              double* dist, hipStream_t st) {
+    if (!ws || !lam0 || !lam_out || !iters || !dist || !a || !P || (!idx && !kp))
+        return fail(AIY_BAD_ARG, "NULL argument (need policy_idx or policy_k)");
+    if (C < 1 || C > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "need 1 <= C < 2^31");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    const bool lottery = idx == nullptr;
+    const size_t n = (size_t)ws->N * ws->Na, nw = n + (size_t)ws->N;
+    const int64_t min_c = ws->dist_batch_min < 0 ? kDistBatchMinC : ws->dist_batch_min;
+    const bool batched = min_c > 0 && C >= min_c && C <= 65535 &&
+                         dist_batch_fits(ws->N, ws->Na, lottery);
+    std::vector<char> separate((size_t)C, 1);  // candidates left to the per-candidate path
+    if (batched) {
+        DistBatchBlocks& bb = ws->dist_batch;
+        AIY_TRY(bb.ensure((size_t)C, n, nw));
+        DistBatchArgs A{};
+        A.N = (int)ws->N; A.Na = (int)ws->Na; A.C = (int)C;
+        A.lottery = lottery; A.tol = tol; A.max_iter = max_iter;
+        A.idx = idx; A.kp = kp; A.a = a; A.P = P; A.lam = lam0; A.out = lam_out;
+        A.key = bb.key; A.off = bb.off; A.wr = bb.wr; A.flags = bb.flags;
+        A.iters = bb.iters; A.dist = bb.dist; A.part = bb.part; A.k = k_dev;
+        AIY_HIP(hipMemsetAsync(bb.flags, 0, sizeof(unsigned) * C, st));
+        AIY_TRY(launch_dist_batch_prepare(A, st));
+        AIY_HIP(hipMemcpyAsync(bb.hflags, bb.flags, sizeof(unsigned) * C, hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipStreamSynchronize(st));
+        int64_t nb = 0;
+        for (int64_t c = 0; c < C; ++c) {
+            if (bb.hflags[c] & 2u)
+                return fail(AIY_BAD_ARG, "candidate %lld: policy index outside [1, Na]",
+                            (long long)c + 1);
+            separate[c] = bb.hflags[c] != 0u;
+            nb += !separate[c];
+        }
+        if (nb > 0) {
+            AIY_TRY(ws_timing_begin(ws, st));
+            AIY_TRY(launch_dist_solve_batch(A, st));
+            AIY_TRY(ws_timing_end(ws, st));
+            ++ws->dist_batch_launches;
+            AIY_HIP(hipMemcpyAsync(bb.hiters, bb.iters, sizeof(long long) * C, hipMemcpyDeviceToHost, st));
+            AIY_HIP(hipMemcpyAsync(bb.hdist, bb.dist, sizeof(double) * C, hipMemcpyDeviceToHost, st));
+            AIY_HIP(hipStreamSynchronize(st));  // the batched path's one synchronisation
+            for (int64_t c = 0; c < C; ++c)
+                if (!separate[c]) {
+                    iters[c] = (int64_t)bb.hiters[c];
+                    dist[c] = bb.hdist[c];
+                }
+        }
+    } else if (idx) {
+        // every candidate's indices are checked before the first solve, as on the batched path
+        for (int64_t c = 0; c < C; ++c) {
+            DistArgs A;
+            bool fb = false;
+            const int rc = dist_plan(ws, idx + c * n, nullptr, a, P, &A, &fb, st);
+            if (rc == AIY_BAD_ARG)
+                return fail(AIY_BAD_ARG, "candidate %lld: policy index outside [1, Na]",
+                            (long long)c + 1);
+            AIY_TRY(rc);
+        }
+    }
+    for (int64_t c = 0; c < C; ++c) {
+        if (!separate[c]) continue;
+        AIY_TRY(dist_stationary_dev(ws, lam0 + c * n, idx ? idx + c * n : nullptr,
+                                    kp && !idx ? kp + c * n : nullptr, a, P, tol, max_iter,
+                                    lam_out + c * n, k_dev ? k_dev + c : nullptr, iters + c,
+                                    dist + c, st));
+        ++ws->dist_batch_fallbacks;
+    }
+    return AIY_OK;
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -260,6 +339,88 @@ int aiy_dist_stationary(const int32_t* policy_idx, const double* policy_k, int v
     else memcpy(lambda, rows.data(), nb);
     *iters = it;
     *dist = d;
+    return AIY_OK;
+}
+
+int aiy_dist_stationary_batch_dev(aiy_ws* ws, int64_t C, const double* lambda,
+                                  const int32_t* policy_idx, const double* policy_k,
+                                  const double* a_grid, const double* P, double tol,
+                                  int64_t max_iter, double* lambda_out, double* k_supply,
+                                  int64_t* iters, double* dist, void* stream) {
+    return dist_stationary_batch_dev(ws, C, lambda, policy_idx, policy_k, a_grid, P, tol, max_iter,
+                                     lambda_out, k_supply, iters, dist, (hipStream_t)stream);
+}
+
+int aiy_ws_set_dist_batch(aiy_ws* ws, int min_candidates) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (min_candidates < -1) return fail(AIY_BAD_ARG, "min_candidates must be >= -1");
+    ws->dist_batch_min = min_candidates;
+    return AIY_OK;
+}
+
+int aiy_ws_dist_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_solves) {
+    if (!ws) return fail(AIY_BAD_ARG, "NULL workspace");
+    if (launches) *launches = ws->dist_batch_launches;
+    if (fallback_solves) *fallback_solves = ws->dist_batch_fallbacks;
+    return AIY_OK;
+}
+
+int aiy_dist_stationary_batch(int64_t C, const int32_t* policy_idx, const double* policy_k,
+                              int vfi_layout, const double* a_grid, const double* P, int64_t N,
+                              int64_t Na, double tol, int64_t max_iter, double* lambda,
+                              double* k_supply, int64_t* iters, double* dist) {
+    if ((!policy_idx && !policy_k) || !P || !lambda || !k_supply || !iters || !dist)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || C > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "need 1 <= C < 2^31");
+    if (N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need N >= 1 and Na >= 2");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    AIY_TRY(!policy_idx ? check_grid_strict(a_grid, Na) : check_grid(a_grid, Na));
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    std::vector<double> s1(N, 1.0);
+    double *da, *ds, *dP, *dl0, *dl1, *dkp = nullptr, *dK;
+    int* didx = nullptr;
+    AIY_TRY(stage_common(c, a_grid, s1.data(), P, N, Na, &da, &ds, &dP));
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    AIY_TRY(c->buf("distb_l0", nb * C, (void**)&dl0));
+    AIY_TRY(c->buf("distb_l1", nb * C, (void**)&dl1));
+    AIY_TRY(c->buf("distb_K", sizeof(double) * C, (void**)&dK));
+    // layouts: vfi_layout → N x Na column-major; else Na x N column-major (== [N][Na])
+    std::vector<double> rows(n * C);
+    auto to_rows = [&](const double* src) {
+        for (int64_t q = 0; q < C; ++q) {
+            if (vfi_layout) cm_to_rows(src + q * n, N, Na, rows.data() + q * n);
+            else memcpy(rows.data() + q * n, src + q * n, nb);
+        }
+    };
+    if (policy_idx) {
+        std::vector<int> ib(n * C);
+        for (int64_t q = 0; q < C; ++q)
+            for (int64_t i = 0; i < N; ++i)
+                for (int64_t j = 0; j < Na; ++j)
+                    ib[q * n + i * Na + j] =
+                        (vfi_layout ? policy_idx[q * n + i + j * N] : policy_idx[q * n + j + i * Na]) - 1;
+        AIY_TRY(c->buf("distb_idx", n * C * sizeof(int), (void**)&didx));
+        AIY_HIP(hipMemcpyAsync(didx, ib.data(), n * C * sizeof(int), hipMemcpyHostToDevice, c->st));
+        AIY_HIP(hipStreamSynchronize(c->st));
+    } else {
+        AIY_TRY(c->buf("distb_kp", nb * C, (void**)&dkp));
+        to_rows(policy_k);
+        AIY_HIP(hipMemcpyAsync(dkp, rows.data(), nb * C, hipMemcpyHostToDevice, c->st));
+        AIY_HIP(hipStreamSynchronize(c->st));
+    }
+    to_rows(lambda);
+    AIY_HIP(hipMemcpyAsync(dl0, rows.data(), nb * C, hipMemcpyHostToDevice, c->st));
+    AIY_TRY(dist_stationary_batch_dev(c->ws, C, dl0, didx, dkp, da, dP, tol, max_iter, dl1, dK,
+                                      iters, dist, c->st));
+    AIY_HIP(hipMemcpyAsync(rows.data(), dl1, nb * C, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(k_supply, dK, sizeof(double) * C, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipStreamSynchronize(c->st));
+    for (int64_t q = 0; q < C; ++q) {
+        if (vfi_layout) rows_to_cm(rows.data() + q * n, N, Na, lambda + q * n);
+        else memcpy(lambda + q * n, rows.data() + q * n, nb);
+    }
     return AIY_OK;
 }
 

@@ -8,6 +8,8 @@
 // aiy_egm_ge_batch is the same for the EGM scripts (Aiyagari_EGM.m:177-242, labour :174-240):
 // the batched EGM solve (aiy_egm_solve_batch_dev) from a common policy_c with the caller's w per
 // candidate; the device split, the uniforms and the chains are shared with aiy_ge_batch.
+// aiy_ge_hist_batch and aiy_egm_ge_hist_batch replace the chains by the stationary histogram (A10)
+// of every candidate's policy in one batched solve (aiy_dist_stationary_batch_dev).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -246,6 +248,113 @@ static int labor_ge_share(GeShare& sh, const double* r, const double* const rows
     return AIY_OK;
 }
 
+// The share's batched histogram supply (A10) on its C policies — idx (on-grid, 0-based) or pk
+// (lottery) [cn][N][Na] — every candidate with skip[q] == 0 (skip nullable) from the common
+// start lam_rows ([N][Na]; NULL: uniform 1/(N·Na)): one batched solve per run of candidates
+// that are not skipped; k_supply and dist_iters of [c0, c0 + cn) back (synchronises).
+static int ge_hist(GeShare& sh, const int* idx, const double* pk, const double* da,
+                   const double* dP, int64_t N, int64_t Na, double dist_tol, int64_t dist_max_iter,
+                   const double* lam_rows, const int32_t* skip, double* k_supply,
+                   int64_t* dist_iters) {
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    double *l0, *l1, *dK;
+    AIY_TRY(c->buf("geh_l0", nb * C, (void**)&l0));
+    AIY_TRY(c->buf("geh_l1", nb * C, (void**)&l1));
+    AIY_TRY(c->buf("geh_K", sizeof(double) * C, (void**)&dK));
+    std::vector<double> uni;
+    if (!lam_rows) {
+        uni.assign(n, 1.0 / (double)(N * Na));
+        lam_rows = uni.data();
+    }
+    AIY_HIP(hipMemcpyAsync(l0, lam_rows, nb, hipMemcpyHostToDevice, c->st));
+    for (int64_t q = 1; q < C; ++q)
+        AIY_HIP(hipMemcpyAsync(l0 + q * n, l0, nb, hipMemcpyDeviceToDevice, c->st));
+    std::vector<double> dist(C);
+    for (int64_t q0 = 0; q0 < C;) {
+        if (skip && skip[q0]) {
+            k_supply[sh.c0 + q0] = NAN;
+            dist_iters[sh.c0 + q0] = 0;
+            ++q0;
+            continue;
+        }
+        int64_t q1 = q0;
+        while (q1 < C && !(skip && skip[q1])) ++q1;
+        AIY_TRY(aiy_dist_stationary_batch_dev(c->ws, q1 - q0, l0 + q0 * n, idx ? idx + q0 * n : nullptr,
+                                              idx ? nullptr : pk + q0 * n, da, dP, dist_tol,
+                                              dist_max_iter, l1 + q0 * n, dK + q0,
+                                              dist_iters + sh.c0 + q0, dist.data() + q0, c->st));
+        AIY_HIP(hipMemcpyAsync(k_supply + sh.c0 + q0, dK + q0, sizeof(double) * (q1 - q0),
+                               hipMemcpyDeviceToHost, c->st));
+        q0 = q1;
+    }
+    AIY_HIP(hipStreamSynchronize(c->st));
+    return AIY_OK;
+}
+
+// one device's share of aiy_ge_hist_batch: ge_share with the chains replaced by the batched
+// histogram on the solve's index policy
+static int ge_hist_share(GeShare& sh, const double* r, const double* v_rows, const double* a,
+                         const double* s, const double* P, int64_t N, int64_t Na, double alpha,
+                         double delta, double beta, double sigma, double tol, int64_t max_iter,
+                         double dist_tol, int64_t dist_max_iter, const double* lam_rows,
+                         double* k_supply, int64_t* iters, int64_t* dist_iters) {
+    AIY_HIP(hipSetDevice(sh.dev));
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    double *da, *ds, *dP, *va, *vb, *pk;
+    int* idx;
+    AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
+    AIY_TRY(c->buf("ge_va", nb * C, (void**)&va));
+    AIY_TRY(c->buf("ge_vb", nb * C, (void**)&vb));
+    AIY_TRY(c->buf("ge_pk", nb * C, (void**)&pk));
+    AIY_TRY(c->buf("ge_idx", sizeof(int) * n * C, (void**)&idx));
+    AIY_HIP(hipMemcpyAsync(va, v_rows, nb, hipMemcpyHostToDevice, c->st));
+    for (int64_t q = 1; q < C; ++q)
+        AIY_HIP(hipMemcpyAsync(va + q * n, va, nb, hipMemcpyDeviceToDevice, c->st));
+    std::vector<double> w(C);
+    for (int64_t q = 0; q < C; ++q)  // Aiyagari_VFI.m:149 (w at the candidate r)
+        w[q] = (1 - alpha) * std::pow(alpha / (r[sh.c0 + q] + delta), alpha / (1 - alpha));
+    std::vector<int> which(C);
+    AIY_TRY(bell_solve_batch_dev(c->ws, C, r + sh.c0, w.data(), va, vb, da, ds, dP, beta, sigma,
+                                 tol, max_iter, 0, idx, pk, nullptr, iters + sh.c0, which.data(),
+                                 c->st));
+    return ge_hist(sh, idx, nullptr, da, dP, N, Na, dist_tol, dist_max_iter, lam_rows, nullptr,
+                   k_supply, dist_iters);
+}
+
+// one device's share of aiy_egm_ge_hist_batch: egm_ge_share with the chains replaced by the
+// batched lottery histogram on policy_k of the candidates that solved
+static int egm_ge_hist_share(GeShare& sh, const double* r, const double* w, const double* pc_start,
+                             const double* a, const double* s, const double* P, int64_t N,
+                             int64_t Na, double beta, double sigma, double amin, int labor,
+                             double phi, double theta, double tol, int64_t max_iter,
+                             double dist_tol, int64_t dist_max_iter, const double* lam_rows,
+                             double* k_supply, int64_t* iters, int64_t* dist_iters,
+                             int32_t* status) {
+    AIY_HIP(hipSetDevice(sh.dev));
+    HostCtx* c = sh.ctx;
+    const int64_t C = sh.cn;
+    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
+    double *da, *ds, *dP, *pc, *pk, *pl = nullptr;
+    AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
+    AIY_TRY(c->buf("ege_pc", nb * C, (void**)&pc));
+    AIY_TRY(c->buf("ge_pk", nb * C, (void**)&pk));
+    if (labor) AIY_TRY(c->buf("ege_pl", nb * C, (void**)&pl));
+    AIY_HIP(hipMemcpyAsync(pc, pc_start, nb, hipMemcpyHostToDevice, c->st));
+    for (int64_t q = 1; q < C; ++q)
+        AIY_HIP(hipMemcpyAsync(pc + q * n, pc, nb, hipMemcpyDeviceToDevice, c->st));
+    std::vector<double> dist(C);
+    int32_t* stq = status + sh.c0;
+    AIY_TRY(aiy_egm_solve_batch_dev(c->ws, C, r + sh.c0, w + sh.c0, pc, da, ds, dP, beta, sigma,
+                                    amin, labor, phi, theta, tol, max_iter, pk, pl,
+                                    iters + sh.c0, dist.data(), stq, c->st));
+    return ge_hist(sh, nullptr, pk, da, dP, N, Na, dist_tol, dist_max_iter, lam_rows, stq, k_supply,
+                   dist_iters);
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -351,6 +460,69 @@ int aiy_egm_ge_batch(const double* r, const double* w, int64_t C, const double* 
         return egm_ge_share(g, r, w, policy_c_start, a_grid, s, P, N, Na, beta, sigma, amin,
                             labor_flag, phi, theta, tol, max_iter, z1, k1, T, uniforms, k_supply,
                             iters, status);
+    }));
+    for (int64_t q = 0; q < C; ++q)  // K_d at the candidate r (Aiyagari_EGM.m:242)
+        k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
+    return AIY_OK;
+}
+
+int aiy_ge_hist_batch(const double* r, int64_t C, const double* v_start, const double* a_grid,
+                      const double* s, const double* P, int64_t N, int64_t Na, double alpha,
+                      double delta, double beta, double sigma, double labor, double tol,
+                      int64_t max_iter, double dist_tol, int64_t dist_max_iter,
+                      const double* lambda_start, int n_devices, double* k_supply,
+                      double* k_demand, int64_t* iters, int64_t* dist_iters) {
+    if (!r || !v_start || !s || !P || !k_supply || !k_demand || !iters || !dist_iters)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need C >= 1, N >= 1, Na >= 2");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    if (dist_max_iter < 1) return fail(AIY_BAD_ARG, "dist_max_iter must be >= 1");
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    for (int64_t q = 0; q < C; ++q)
+        if (!std::isfinite(r[q]) || r[q] + delta <= 0)
+            return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
+    std::vector<double> rows((size_t)N * Na), lrows;
+    cm_to_rows(v_start, N, Na, rows.data());
+    if (lambda_start) {
+        lrows.resize((size_t)N * Na);
+        cm_to_rows(lambda_start, N, Na, lrows.data());
+    }
+    AIY_TRY(ge_run_shares(C, N, Na, 1, n_devices, [&](GeShare& g) {
+        return ge_hist_share(g, r, rows.data(), a_grid, s, P, N, Na, alpha, delta, beta, sigma, tol,
+                             max_iter, dist_tol, dist_max_iter,
+                             lambda_start ? lrows.data() : nullptr, k_supply, iters, dist_iters);
+    }));
+    for (int64_t q = 0; q < C; ++q)  // Aiyagari_VFI.m:195
+        k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));
+    return AIY_OK;
+}
+
+int aiy_egm_ge_hist_batch(const double* r, const double* w, int64_t C,
+                          const double* policy_c_start, const double* a_grid, const double* s,
+                          const double* P, int64_t N, int64_t Na, double alpha, double delta,
+                          double beta, double sigma, double amin, int labor_flag, double phi,
+                          double theta, double labor, double tol, int64_t max_iter,
+                          double dist_tol, int64_t dist_max_iter, const double* lambda_start,
+                          int n_devices, double* k_supply, double* k_demand, int64_t* iters,
+                          int64_t* dist_iters, int32_t* status) {
+    if (!r || !w || !policy_c_start || !s || !P || !k_supply || !k_demand || !iters ||
+        !dist_iters || !status)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need C >= 1, N >= 1, Na >= 2");
+    if (N > 16) return fail(AIY_BAD_SHAPE, "EGM kernels support N <= 16 productivity states");
+    if (max_iter < 1) return fail(AIY_BAD_ARG, "max_iter must be >= 1");
+    if (dist_max_iter < 1) return fail(AIY_BAD_ARG, "dist_max_iter must be >= 1");
+    if (labor_flag && !(std::isfinite(phi) && std::isfinite(theta)))
+        return fail(AIY_NON_FINITE, "phi and theta must be finite");
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    for (int64_t q = 0; q < C; ++q)
+        if (!std::isfinite(r[q]) || r[q] + delta <= 0)
+            return fail(AIY_BAD_ARG, "candidate %lld: r must be finite with r + delta > 0", (long long)q + 1);
+    // lambda_start Na x N column-major == [N][Na]
+    AIY_TRY(ge_run_shares(C, N, Na, 1, n_devices, [&](GeShare& g) {
+        return egm_ge_hist_share(g, r, w, policy_c_start, a_grid, s, P, N, Na, beta, sigma, amin,
+                                 labor_flag, phi, theta, tol, max_iter, dist_tol, dist_max_iter,
+                                 lambda_start, k_supply, iters, dist_iters, status);
     }));
     for (int64_t q = 0; q < C; ++q)  // K_d at the candidate r (Aiyagari_EGM.m:242)
         k_demand[q] = labor * std::pow(alpha / (r[q] + delta), 1 / (1 - alpha));

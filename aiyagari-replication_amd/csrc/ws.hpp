@@ -156,6 +156,12 @@ struct aiy_ws {
     int labor_batch_min = 0;
     aiy::LaborBatchBlocks labor_batch;
     int64_t labor_batch_solves = 0, labor_batch_fallbacks = 0;
+    // batched histogram solve (aiy_dist_stationary_batch_dev; aiy_ws_set_dist_batch): the
+    // one-launch path from dist_batch_min candidates on (-1: kDistBatchMinC, 0: never), its
+    // blocks, and how often each path ran on this workspace (aiy_ws_dist_batch_counts)
+    int dist_batch_min = -1;
+    aiy::DistBatchBlocks dist_batch;
+    int64_t dist_batch_launches = 0, dist_batch_fallbacks = 0;
     // timing of the dominant kernel
     bool timing = false, count_hits = false;
     aiy::Events ev_start, ev_stop;

@@ -263,19 +263,29 @@ def auto_levels(world: int) -> int:
 
 
 def aiyagari_vfi_multisection(Na=400, levels=None, rank=0, world=1, allgather=None, r0=0.04,
-                              shocks="tauchen", batched=True):
+                              shocks="tauchen", batched=True, supply="mc"):
     """Config 4: the GE of Aiyagari_VFI.m with candidate rates spread over `world` ranks.
     Every rank solves r0 once (the common warm start), then the rounds; batched=True evaluates
     each rank's nodes of a round in one batched device call (else one solve after another).
-    levels=None picks auto_levels(world); BASELINE's 64-candidate configuration is levels=6."""
+    levels=None picks auto_levels(world); BASELINE's 64-candidate configuration is levels=6.
+    supply="histogram": K_s from the stationary histogram (A10) of each candidate's policy, a
+    round's histograms in one batched solve (hip_hist_batch_evaluator), in place of the chains."""
+    if supply not in ("mc", "histogram"):
+        raise ValueError(f"supply must be 'mc' or 'histogram', not {supply!r}")
     levels = auto_levels(world) if levels is None else levels
     from . import calibration as cb
     from .vfi import vfi_solve
     cal = cb.aiyagari(Na=Na, shocks=shocks)
     R0 = vfi_solve(np.zeros((cal["N"], Na)), cal["a_grid"], cal["s"], cal["P"], r0,
                    cb.wage(r0, cal["alpha"], cal["delta"]), cal["beta"], cal["sigma"])
-    ev = (hip_batch_evaluator if batched else hip_vfi_evaluator)(cal, R0["v_old"])
     lo, hi = -0.05, 1 / cal["beta"] - 1
+    if supply == "histogram":
+        import functools
+        ev = (hip_hist_batch_evaluator if batched else hip_hist_evaluator)(cal, R0["v_old"])
+        if allgather is None and world > 1:
+            allgather = functools.partial(torch_allgather, fields=5)
+        return multisection(ev, lo, hi, levels=levels, rank=rank, world=world, allgather=allgather)
+    ev = (hip_batch_evaluator if batched else hip_vfi_evaluator)(cal, R0["v_old"])
     return multisection(ev, lo, hi, levels=levels, rank=rank, world=world,
                         allgather=allgather if allgather else (torch_allgather if world > 1 else None))
 
@@ -391,14 +401,19 @@ def hip_egm_batch_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, ma
 
 
 def aiyagari_egm_multisection(Na=400, labor=False, levels=None, rank=0, world=1, allgather=None,
-                              batched=True, T=10000, tol=1e-5, max_iter=1000, phi=1.0, theta=1.0):
+                              batched=True, T=10000, tol=1e-5, max_iter=1000, phi=1.0, theta=1.0,
+                              supply="mc"):
     """The GE of Aiyagari_EGM.m (labor: Aiyagari_Endogenous_Labor_EGM.m) with the candidate
     rates of the next `levels` bisection steps evaluated at once.  Every rank solves r0 = 0.04
     from the :64 guess, then the rounds, every candidate from that policy at the scripts' stale
     w; batched=True runs a round's nodes of this rank in one aiy_egm_ge_batch call.  The scripts'
-    chained warm start takes the same bracket decisions (tests/test_egm_batch_gpu.py)."""
+    chained warm start takes the same bracket decisions (tests/test_egm_batch_gpu.py).
+    supply="histogram": K_s from the lottery histogram (A10) of each candidate's policy_k, a
+    round's histograms in one batched solve (hip_egm_hist_batch_evaluator)."""
     import functools
     from .egm import egm_solve, labor_egm_solve
+    if supply not in ("mc", "histogram"):
+        raise ValueError(f"supply must be 'mc' or 'histogram', not {supply!r}")
     levels = auto_levels(world) if levels is None else levels
     cal, r0, w, guess = egm_calibration(Na, labor)
     a, s, P = cal["a_grid"], cal["s"], cal["P"]
@@ -409,16 +424,181 @@ def aiyagari_egm_multisection(Na=400, labor=False, levels=None, rank=0, world=1,
         R0 = egm_solve(guess.T, a, s, P, r0, w, cal["beta"], cal["sigma"], cal["amin"], tol,
                        max_iter)
     pc0 = np.ascontiguousarray(R0["policy_c"].T)
-    if batched:
+    if supply == "histogram":
+        ev = (hip_egm_hist_batch_evaluator if batched else hip_egm_hist_evaluator)(
+            cal, pc0, w, labor, tol, max_iter, phi=phi, theta=theta)
+    elif batched:
         ev = hip_egm_batch_evaluator(cal, pc0, w, labor, T, tol, max_iter, 1, phi, theta)
     else:
         ev = hip_egm_evaluator(cal, pc0, w, labor, T, tol, max_iter, phi, theta)
     if allgather is None and world > 1:
-        allgather = functools.partial(torch_allgather, fields=4)
+        allgather = functools.partial(torch_allgather, fields=5 if supply == "histogram" else 4)
     tr = multisection(ev, -0.05, 1 / cal["beta"] - 1, levels=levels, rank=rank, world=world,
                       allgather=allgather)
     tr.iters = [int(R0["iters"])] + tr.iters
     return tr
+
+
+# --------------------------------------------- the histogram supply (A10) in the GE rounds
+# the stopping rule ge.py's supply="histogram" uses
+HIST_TOL, HIST_MAX_ITER = 1e-13, 100000
+
+
+def hist_evaluator(cal, solve, supply, start):
+    """Node evaluator with the stationary histogram (A10) as the supply estimator: no sampling
+    noise, so a node's result depends on its rate alone.  Generic in the two callables (the GPU
+    path or the C oracle): solve(start, r) -> dict(iters[, status], the policy) from the
+    path-independent warm start (the callable fixes the wage: Aiyagari_VFI.m's follows r, the EGM
+    scripts keep theirs); supply(R) -> (K_s, pushes) on that policy.  Results are
+    (K_s, K_d, iters, status, dist_iters); K_s is NaN and dist_iters 0 where status != 0."""
+    from . import calibration as cb
+
+    def evaluate(node):
+        R = solve(start, node.r)
+        st = int(R.get("status", 0))
+        Ks, pushes = (math.nan, 0) if st else supply(R)
+        Kd = cb.capital_demand(node.r, cal["labor"], cal["alpha"], cal["delta"])
+        return (float(Ks), float(Kd), int(R["iters"]), st, int(pushes))
+    return evaluate
+
+
+def hip_hist_evaluator(cal, v_start, tol=1e-5, max_iter=1000, dist_tol=HIST_TOL,
+                       dist_max_iter=HIST_MAX_ITER, lam_start=None):
+    """hist_evaluator on this rank's GPU, one VFI solve and one histogram after another."""
+    from . import calibration as cb
+    from .dist import dist_stationary
+    from .vfi import vfi_solve
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+
+    def solve(v, r):
+        return vfi_solve(v, a, s, P, r, cb.wage(r, cal["alpha"], cal["delta"]), cal["beta"],
+                         cal["sigma"], tol, max_iter)
+
+    def supply(R):
+        _, K, it, _ = dist_stationary(a, P, policy_idx=R["idx"], lam0=lam_start, tol=dist_tol,
+                                      max_iter=dist_max_iter)
+        return K, it
+    return hist_evaluator(cal, solve, supply, v_start)
+
+
+def hip_egm_hist_evaluator(cal, pc_start, w, labor=False, tol=1e-5, max_iter=1000,
+                           dist_tol=HIST_TOL, dist_max_iter=HIST_MAX_ITER, lam_start=None, phi=1.0,
+                           theta=1.0):
+    """hist_evaluator on this rank's GPU for the EGM scripts (pc_start, lam_start [N][Na]), one
+    solve and one lottery histogram after another."""
+    from ._capi import AiyError
+    from .dist import dist_stationary
+    from .egm import egm_solve, labor_egm_solve
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+
+    def solve(pc, r):
+        try:
+            if labor:
+                return labor_egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], phi, theta,
+                                       cal["amin"], tol, max_iter)
+            return egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], cal["amin"], tol,
+                             max_iter)
+        except AiyError as e:
+            if "not increasing" not in str(e):
+                raise
+            return dict(policy_k=None, iters=0, status=1)
+
+    def supply(R):
+        _, K, it, _ = dist_stationary(a, P, policy_k=R["policy_k"],
+                                      lam0=None if lam_start is None else np.asarray(lam_start).T,
+                                      tol=dist_tol, max_iter=dist_max_iter, vfi_layout=False)
+        return K, it
+    return hist_evaluator(cal, solve, supply, pc_start)
+
+
+def ge_hist_batch_call(r, v_start, cal, tol=1e-5, max_iter=1000, dist_tol=HIST_TOL,
+                       dist_max_iter=HIST_MAX_ITER, lam_start=None, n_devices=1):
+    """aiy_ge_hist_batch (C ABI): K_s (histogram), K_d, VFI sweeps and pushes at every rate in
+    `r`, each from v_start and lam_start (N x Na; None: uniform)."""
+    from ._capi import check, d, i64, ip, lib, ptr
+    r = np.ascontiguousarray(r, np.float64)
+    n = r.size
+    N, Na = cal["N"], cal["Na"]
+    v = np.asfortranarray(v_start, dtype=np.float64)
+    lam = None if lam_start is None else np.asfortranarray(lam_start, dtype=np.float64)
+    if lam is not None and lam.shape != (N, Na):
+        raise ValueError(f"lam_start must be (N, Na) = {(N, Na)}")
+    a = np.ascontiguousarray(cal["a_grid"], np.float64)
+    s = np.ascontiguousarray(cal["s"], np.float64)
+    P = np.asfortranarray(cal["P"], dtype=np.float64)
+    Ks, Kd = np.empty(n), np.empty(n)
+    it, dit = np.empty(n, np.int64), np.empty(n, np.int64)
+    check(lib().aiy_ge_hist_batch(ptr(r), i64(n), ptr(v), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
+                                  d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
+                                  d(cal["sigma"]), d(cal["labor"]), d(tol), i64(max_iter),
+                                  d(dist_tol), i64(dist_max_iter), ptr(lam), ip(n_devices),
+                                  ptr(Ks), ptr(Kd), ptr(it), ptr(dit)))
+    return Ks, Kd, it, dit
+
+
+def egm_ge_hist_batch_call(r, w, pc_start, cal, labor=False, phi=1.0, theta=1.0, tol=1e-5,
+                           max_iter=1000, dist_tol=HIST_TOL, dist_max_iter=HIST_MAX_ITER,
+                           lam_start=None, n_devices=1):
+    """aiy_egm_ge_hist_batch (C ABI): K_s (lottery histogram), K_d, EGM steps, pushes and status
+    at every rate in `r`, each from pc_start and lam_start ([N][Na]; None: uniform) at wage w
+    (a scalar or one per rate)."""
+    from ._capi import check, d, i64, ip, lib, ptr
+    r = np.ascontiguousarray(r, np.float64)
+    n = r.size
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
+    N, Na = cal["N"], cal["Na"]
+    pc = np.ascontiguousarray(pc_start, np.float64)  # [N][Na] == the script's Na x N
+    lam = None if lam_start is None else np.ascontiguousarray(lam_start, np.float64)
+    if pc.shape != (N, Na) or (lam is not None and lam.shape != (N, Na)):
+        raise ValueError(f"pc_start and lam_start must be [N][Na] = {(N, Na)}")
+    a = np.ascontiguousarray(cal["a_grid"], np.float64)
+    s = np.ascontiguousarray(cal["s"], np.float64)
+    P = np.asfortranarray(cal["P"], dtype=np.float64)
+    Ks, Kd = np.empty(n), np.empty(n)
+    it, dit, st = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.int32)
+    check(lib().aiy_egm_ge_hist_batch(ptr(r), ptr(w), i64(n), ptr(pc), ptr(a), ptr(s), ptr(P),
+                                      i64(N), i64(Na), d(cal["alpha"]), d(cal["delta"]),
+                                      d(cal["beta"]), d(cal["sigma"]), d(cal["amin"]),
+                                      ip(1 if labor else 0), d(phi), d(theta), d(cal["labor"]),
+                                      d(tol), i64(max_iter), d(dist_tol), i64(dist_max_iter),
+                                      ptr(lam), ip(n_devices), ptr(Ks), ptr(Kd), ptr(it), ptr(dit),
+                                      ptr(st)))
+    return Ks, Kd, it, dit, st
+
+
+def hip_hist_batch_evaluator(cal, v_start, tol=1e-5, max_iter=1000, dist_tol=HIST_TOL,
+                             dist_max_iter=HIST_MAX_ITER, lam_start=None, n_devices=1):
+    """hist_evaluator on the batched device path: all of a round's nodes of this rank in one
+    aiy_ge_hist_batch call (one batched VFI solve and one batched histogram solve per GPU).
+    Same per-node arithmetic as hip_hist_evaluator, so the traces are identical."""
+    def many(nodes):
+        Ks, Kd, it, dit = ge_hist_batch_call([n.r for n in nodes], v_start, cal, tol, max_iter,
+                                             dist_tol, dist_max_iter, lam_start, n_devices)
+        return [(float(Ks[q]), float(Kd[q]), int(it[q]), 0, int(dit[q]))
+                for q in range(len(nodes))]
+
+    def evaluate(node):
+        return many([node])[0]
+    evaluate.many = many
+    return evaluate
+
+
+def hip_egm_hist_batch_evaluator(cal, pc_start, w, labor=False, tol=1e-5, max_iter=1000,
+                                 dist_tol=HIST_TOL, dist_max_iter=HIST_MAX_ITER, lam_start=None,
+                                 n_devices=1, phi=1.0, theta=1.0):
+    """The same for the EGM scripts: one aiy_egm_ge_hist_batch call per round (one launch of the
+    solves and one of the lottery histograms per GPU)."""
+    def many(nodes):
+        Ks, Kd, it, dit, st = egm_ge_hist_batch_call([n.r for n in nodes], w, pc_start, cal, labor,
+                                                     phi, theta, tol, max_iter, dist_tol,
+                                                     dist_max_iter, lam_start, n_devices)
+        return [(float(Ks[q]), float(Kd[q]), int(it[q]), int(st[q]), int(dit[q]))
+                for q in range(len(nodes))]
+
+    def evaluate(node):
+        return many([node])[0]
+    evaluate.many = many
+    return evaluate
 
 
 # ------------------------------------------------------- the labour VFI script (E2)

@@ -142,6 +142,17 @@ class Workspace:
         check(lib().aiy_ws_labor_batch_counts(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_dist_batch(self, min_candidates: int = -1):
+        """The batched histogram solve's one-launch path from `min_candidates` on (-1: the
+        measured default, 1: whenever the shape fits, 0: never); results do not depend on it."""
+        check(lib().aiy_ws_set_dist_batch(self._h, ip(min_candidates)))
+
+    def dist_batch_counts(self):
+        """(one-launch batches, per-candidate solves) of dist_stationary_batch_dev so far."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib().aiy_ws_dist_batch_counts(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_variant(self, variant: int):
         """Screen-kernel geometry (tuning; results identical), see aiy_ws_set_variant."""
         check(lib().aiy_ws_set_variant(self._h, ip(variant)))

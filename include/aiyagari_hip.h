@@ -125,6 +125,15 @@ int aiy_dist_stationary(const int32_t* policy_idx, const double* policy_k, int v
                         double tol, int64_t max_iter, double* lambda, double* k_supply,
                         int64_t* iters, double* dist);
 
+/* A10 at C candidate policies (one GE round's supplies): candidate c's policy and lambda are
+ * block c of policy_idx / policy_k and lambda (each block laid out as in aiy_dist_stationary);
+ * lambda in (the candidate's start) / out, k_supply, iters, dist: host [C].  Every candidate's
+ * results equal one aiy_dist_stationary call's bit for bit (aiy_dist_stationary_batch_dev). */
+int aiy_dist_stationary_batch(int64_t C, const int32_t* policy_idx, const double* policy_k,
+                              int vfi_layout, const double* a_grid, const double* P, int64_t N,
+                              int64_t Na, double tol, int64_t max_iter, double* lambda,
+                              double* k_supply, int64_t* iters, double* dist);
+
 /* Config 4 / SURVEY B2 `ge_batch` — excess demand at C candidate rates: for each r(c) the
  * body of one GE step of Aiyagari_VFI.m:147-195: the VFI from v_start (N x Na, the common warm
  * start) to tol, the Monte-Carlo capital supply from (z1 1-based, k1) with the candidate's own
@@ -173,6 +182,30 @@ int aiy_labor_ge_batch(const double* r, int64_t C, const double* v_start,
                        double psi, double eta, double labor, double tol, int64_t max_iter,
                        int64_t z1, double k1, int64_t T, const double* uniforms, int n_devices,
                        double* k_supply, double* k_demand, int64_t* iters);
+
+/* The histogram supply (A10) in place of the Monte-Carlo chains: aiy_ge_batch with K_s of
+ * candidate c = Σ λ_c·a, λ_c the stationary distribution of the solve's index policy iterated
+ * from lambda_start (N x Na column-major, the common start; NULL: uniform 1/(N·Na)) until
+ * max|Δλ| < dist_tol or dist_max_iter pushes — one batched VFI solve and one batched histogram
+ * solve (aiy_dist_stationary_batch_dev) per device.  Out (C each): k_supply, k_demand, iters
+ * (VFI sweeps), dist_iters (pushes). */
+int aiy_ge_hist_batch(const double* r, int64_t C, const double* v_start, const double* a_grid,
+                      const double* s, const double* P, int64_t N, int64_t Na, double alpha,
+                      double delta, double beta, double sigma, double labor, double tol,
+                      int64_t max_iter, double dist_tol, int64_t dist_max_iter,
+                      const double* lambda_start, int n_devices, double* k_supply,
+                      double* k_demand, int64_t* iters, int64_t* dist_iters);
+/* The same for the EGM scripts: aiy_egm_ge_batch with the lottery histogram on the solve's
+ * policy_k (lambda_start Na x N, nullable).  A candidate with status 1 is skipped: k_supply NaN,
+ * dist_iters 0. */
+int aiy_egm_ge_hist_batch(const double* r, const double* w, int64_t C,
+                          const double* policy_c_start, const double* a_grid, const double* s,
+                          const double* P, int64_t N, int64_t Na, double alpha, double delta,
+                          double beta, double sigma, double amin, int labor_flag, double phi,
+                          double theta, double labor, double tol, int64_t max_iter,
+                          double dist_tol, int64_t dist_max_iter, const double* lambda_start,
+                          int n_devices, double* k_supply, double* k_demand, int64_t* iters,
+                          int64_t* dist_iters, int32_t* status);
 
 /* A6 — replaces Krusell_Smith_VFI.m:149-168 (policy improvement with fminbnd).
  * value, k_opt: k x K x S column-major (S = 4); B 4; P 4 x 4; params = 13 doubles {beta, alpha,
@@ -487,6 +520,28 @@ int aiy_dist_stationary_dev(aiy_ws* ws, const double* lambda, const int32_t* pol
                             const double* policy_k, const double* a_grid, const double* P,
                             double tol, int64_t max_iter, double* lambda_out,
                             double* k_supply, int64_t* iters, double* dist, void* stream);
+/* A10 at C candidate policies on device: candidate c's fixed point from lambda[c] on
+ * policy_idx[c] (0-based) or policy_k[c] (lottery) — all device [C][N][Na] — into lambda_out[c];
+ * k_supply (nullable): device [C]; iters, dist: host [C].  For every candidate λ, K, iters and
+ * dist equal one aiy_dist_stationary_dev call's bit for bit.  Where a candidate's arrays fit one
+ * CU's LDS (N <= 16 and 8·N·Na·(2 + lottery) + 4·N·(Na+1) + 2.2 KB within 160 KiB) and C is at
+ * least the workspace's threshold (aiy_ws_set_dist_batch), one prepare launch pair builds all
+ * plans, their flags are read once, and ONE launch runs one workgroup per monotone candidate
+ * with the whole loop in LDS, followed by one synchronisation.  A non-monotone candidate — and
+ * every candidate otherwise — runs through the per-candidate solve.  An index outside [1, Na]
+ * in any candidate: AIY_BAD_ARG naming the candidate (1-based), before any solve. */
+int aiy_dist_stationary_batch_dev(aiy_ws* ws, int64_t C, const double* lambda,
+                                  const int32_t* policy_idx, const double* policy_k,
+                                  const double* a_grid, const double* P, double tol,
+                                  int64_t max_iter, double* lambda_out, double* k_supply,
+                                  int64_t* iters, double* dist, void* stream);
+/* the batched histogram solve's dispatch on this workspace: the one-launch path from
+ * min_candidates on (-1, the default: the measured threshold; 1: whenever the
+ * shape fits; 0: never).  Results do not depend on it. */
+int aiy_ws_set_dist_batch(aiy_ws* ws, int min_candidates);
+/* how often aiy_dist_stationary_batch_dev took the one-launch path on this workspace, and how
+ * many candidates it solved one by one (both nullable) */
+int aiy_ws_dist_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_solves);
 
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
