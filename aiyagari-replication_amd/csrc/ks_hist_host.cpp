@@ -1,0 +1,134 @@
+// F2 histogram entry points: ks_simulate_hist (MATLAB layouts, synchronous) and its device tier
+// ks_simulate_hist_dev.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "aiy_common.hpp"
+#include "host_ctx.hpp"
+#include "ks_hist.hpp"
+#include "ks_panel.hpp"
+
+namespace aiy {
+
+static int check_hist_shape(int64_t nk, int64_t nK, int64_t nx, int64_t T, int64_t M) {
+    if (T < 2 || T > (1ll << 30)) return fail(AIY_BAD_SHAPE, "T must be in [2, 2^30]");
+    if (M < 1 || M > kHistMaxPaths) return fail(AIY_BAD_SHAPE, "need 1 <= M <= 65,535 shock paths");
+    if (!ks_hist_fits(nx, nk, nK))
+        return fail(AIY_BAD_SHAPE,
+                    "histogram simulation: need nx, k_size, K_size >= 2 and a path's state "
+                    "inside one CU's LDS: 8*(8*nx + K_size + 8) + 4*(5*nx + 4) <= 160 KiB");
+    return AIY_OK;
+}
+
+static int check_hist_params(const double* params) {
+    for (int q = 0; q < 13; ++q)
+        if (!std::isfinite(params[q])) return fail(AIY_NON_FINITE, "non-finite params");
+    const double ug = params[5], ub = params[6];
+    if (!(ug > 0 && ug < 1 && ub > 0 && ub < 1))
+        return fail(AIY_BAD_ARG, "ug and ub must lie in (0, 1)");
+    return AIY_OK;
+}
+
+int hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
+             const double* k_opt, const double* x_grid, int64_t nx, const double* params,
+             const int8_t* zi, int64_t T, int64_t M, double* lam, double* K_ts, int64_t* slow,
+             hipStream_t st) {
+    if (!k_grid || !K_grid || !k_opt || !x_grid || !params || !zi || !lam || !K_ts)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_hist_shape(nk, nK, nx, T, M));
+    AIY_TRY(check_hist_params(params));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(AIY_NO_DEVICE, "no HIP device visible");
+    ShockArgs S{};
+    shock_probs(params[5], params[6], S);
+    HistArgs A{};
+    A.nx = (int)nx;
+    A.nk = (int)nk;
+    A.nK = (int)nK;
+    A.T = (int)T;
+    A.M = (int)M;
+    for (int q = 0; q < 8; ++q) A.thr[q] = S.thr[q];
+    A.k_grid = k_grid;
+    A.K_grid = K_grid;
+    A.x = x_grid;
+    A.k_opt = k_opt;
+    A.zi = zi;
+    A.lam = lam;
+    A.K_ts = K_ts;
+    A.slow = slow;
+    return launch_ks_hist(A, st);
+}
+
+}  // namespace aiy
+
+using namespace aiy;
+
+extern "C" {
+
+int ks_simulate_hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
+                         const double* k_opt, const double* x_grid, int64_t nx,
+                         const double* params, const int8_t* zi, int64_t T, int64_t M,
+                         double* lam, double* K_ts, int64_t* slow_periods, void* stream) {
+    return hist_dev(nk, nK, k_grid, K_grid, k_opt, x_grid, nx, params, zi, T, M, lam, K_ts,
+                    slow_periods, (hipStream_t)stream);
+}
+
+int ks_simulate_hist(const double* k_opt, const double* k_grid, const double* K_grid, int64_t nk,
+                     int64_t nK, const double* x_grid, int64_t nx, const double* params,
+                     const double* zi_shock, int64_t T, int64_t M, double* lam, double* K_ts,
+                     int64_t* slow_periods) {
+    if (!k_opt || !k_grid || !K_grid || !x_grid || !params || !zi_shock || !lam || !K_ts)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_hist_shape(nk, nK, nx, T, M));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // all three are interpolated
+    AIY_TRY(check_grid_strict(K_grid, nK));
+    AIY_TRY(check_grid_strict(x_grid, nx));
+    AIY_TRY(check_hist_params(params));
+    const size_t nko = (size_t)nk * nK * 4, nl = (size_t)2 * nx * M, nz = (size_t)T * M;
+    for (size_t q = 0; q < nko; ++q)
+        if (!std::isfinite(k_opt[q])) return fail(AIY_NON_FINITE, "non-finite k_opt");
+    for (size_t q = 0; q < nl; ++q)
+        if (!std::isfinite(lam[q])) return fail(AIY_NON_FINITE, "non-finite lam");
+    // T x M column-major: path m's chain is contiguous, the device tier's [M][T]
+    std::vector<int8_t> hz(nz);
+    for (size_t q = 0; q < nz; ++q) {
+        if (zi_shock[q] != 0 && zi_shock[q] != 1)
+            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
+        hz[q] = (int8_t)zi_shock[q];
+    }
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
+    double *dko, *dkg, *dKg, *dx, *dlam, *dKts;
+    int64_t* dslow;
+    int8_t* dz;
+    AIY_TRY(c->buf("ksh_kopt", sizeof(double) * nko, (void**)&dko));
+    AIY_TRY(c->buf("ksh_kg", sizeof(double) * nk, (void**)&dkg));
+    AIY_TRY(c->buf("ksh_Kg", sizeof(double) * nK, (void**)&dKg));
+    AIY_TRY(c->buf("ksh_x", sizeof(double) * nx, (void**)&dx));
+    AIY_TRY(c->buf("ksh_lam", sizeof(double) * nl, (void**)&dlam));
+    AIY_TRY(c->buf("ksh_Kts", sizeof(double) * nz, (void**)&dKts));
+    AIY_TRY(c->buf("ksh_slow", sizeof(int64_t) * M, (void**)&dslow));
+    AIY_TRY(c->buf("ksh_zi", nz, (void**)&dz));
+    AIY_HIP(hipMemcpyAsync(dko, k_opt, sizeof(double) * nko, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dkg, k_grid, sizeof(double) * nk, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dKg, K_grid, sizeof(double) * nK, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dx, x_grid, sizeof(double) * nx, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dlam, lam, sizeof(double) * nl, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dz, hz.data(), nz, hipMemcpyHostToDevice, c->st));
+    AIY_TRY(hist_dev(nk, nK, dkg, dKg, dko, dx, nx, params, dz, T, M, dlam, dKts, dslow, c->st));
+    AIY_HIP(hipMemcpyAsync(lam, dlam, sizeof(double) * nl, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(K_ts, dKts, sizeof(double) * nz, hipMemcpyDeviceToHost, c->st));
+    std::vector<int64_t> hs(M);
+    AIY_HIP(hipMemcpyAsync(hs.data(), dslow, sizeof(int64_t) * M, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipStreamSynchronize(c->st));
+    if (slow_periods)
+        for (int64_t m = 0; m < M; ++m) slow_periods[m] = hs[m];
+    return AIY_OK;
+}
+
+}  // extern "C"

@@ -25,6 +25,9 @@ struct ShockArgs {
     int64_t ts, is;
 };
 int launch_ks_shocks(const ShockArgs& A, hipStream_t st);
+// pgg, pbb, ug and thr of Krusell_Smith_VFI.m:24-45 (ks_panel_host.cpp; the histogram
+// simulation mixes employment with the same thr)
+void shock_probs(double ug, double ub, ShockArgs& A);
 
 struct PanelArgs {
     int nk, nK, T, pop, G;

@@ -14,7 +14,7 @@ namespace aiy {
 
 // Krusell_Smith_VFI.m:24-45, the same expressions in the same order as the script (the
 // durations 8, 1.5, 2.5 and the ratios 1.25, 0.75 are literals there, not parameters).
-static void shock_probs(double ug, double ub, ShockArgs& A) {
+void shock_probs(double ug, double ub, ShockArgs& A) {
     const double pgg = 1 - 1 / 8.0, pbb = 1 - 1 / 8.0;
     const double p00_gg = 1 - 1 / 1.5, p00_bb = 1 - 1 / 2.5;
     const double p00_gb = 1.25 * p00_bb, p00_bg = 0.75 * p00_gg;

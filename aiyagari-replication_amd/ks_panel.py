@@ -98,6 +98,129 @@ class PanelSim:
         return self.K_ts
 
 
+# ------------------------------------------------------------------ histogram simulation
+
+
+def hist_grid(nx=1000, k_min=0.0001, k_max=1000.0):
+    """The histogram grid: linspace(0, 1, nx)^7 * (k_max - k_min) + k_min with the end points
+    set exactly (the spacing rule of the script's k_grid, :16-17)."""
+    x = (np.arange(nx) / (nx - 1.0)) ** 7 * (k_max - k_min) + k_min
+    x[0], x[-1] = k_min, k_max
+    return x
+
+
+def hist_start(x_grid, K0, ug):
+    """lam0 (2, nx): all mass at K0 by the lottery between its bracketing nodes, split
+    (1 - ug, ug) over employment (row 0 employed, row 1 unemployed)."""
+    x = np.asarray(x_grid, np.float64)
+    K0 = min(max(float(K0), x[0]), x[-1])
+    j = int(np.clip(np.searchsorted(x, K0, side="right") - 1, 0, x.size - 2))
+    w = (K0 - x[j]) / (x[j + 1] - x[j])
+    lam = np.zeros((2, x.size))
+    for e, pe in ((0, 1 - ug), (1, ug)):
+        lam[e, j] = pe * (1 - w)
+        lam[e, j + 1] = pe * w
+    return lam
+
+
+def zi_paths(T, M, uniforms, params):
+    """M aggregate shock paths (T, M) in {0 good, 1 bad}: the chain of :59-68 on M consecutive
+    blocks of T-1 draws (path 0 on the stream's first T-1 draws is ks_shocks' zi)."""
+    U = np.asarray(uniforms, np.float64).ravel()
+    if U.size < M * (T - 1):
+        raise ValueError(f"need {M * (T - 1)} uniforms, got {U.size}")
+    pgg = 1 - 1 / 8.0
+    pbb = 1 - 1 / 8.0
+    zi = np.zeros((T, M), np.int8)
+    for m in range(M):
+        u = U[m * (T - 1):(m + 1) * (T - 1)]
+        z = 0
+        for t in range(1, T):
+            z = int(u[t - 1] > (pbb if z else pgg))
+            zi[t, m] = z
+    return zi
+
+
+def _hist_shapes(k_opt, k_grid, K_grid, x_grid):
+    nk, nK, nS = k_opt.shape
+    if nS != 4:
+        raise ValueError("k_opt must be k x K x 4")
+    if k_grid.size != nk or K_grid.size != nK:
+        raise ValueError("k_opt must be numel(k_grid) x numel(K_grid) x 4")
+    return nk, nK, x_grid.size
+
+
+def ks_simulate_hist(k_opt, k_grid, K_grid, x_grid, zi_paths, lam0, params):
+    """The histogram simulation of the capital path through the host tier.  k_opt k x K x 4;
+    zi_paths (T, M) in {0, 1}; lam0 (M, 2, nx) or (2, nx) (every path starts from it).
+    Returns (K_ts (T, M), lam (M, 2, nx), slow_periods (M,))."""
+    ko = np.asfortranarray(k_opt, dtype=np.float64)
+    kg = np.ascontiguousarray(k_grid, np.float64)
+    Kg = np.ascontiguousarray(K_grid, np.float64)
+    x = np.ascontiguousarray(x_grid, np.float64)
+    nk, nK, nx = _hist_shapes(ko, kg, Kg, x)
+    zi = np.asarray(zi_paths, np.float64)
+    zi = zi[:, None] if zi.ndim == 1 else zi
+    T, M = zi.shape
+    zi = np.asfortranarray(zi)
+    lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (M, 2, nx)), order="C")
+    prm = np.ascontiguousarray(params, np.float64)
+    if prm.size != 13:
+        raise ValueError("params must hold the 13 KS doubles")
+    K_ts = np.empty((T, M), order="F")
+    slow = np.zeros(M, np.int64)
+    check(lib().ks_simulate_hist(ptr(ko), ptr(kg), ptr(Kg), i64(nk), i64(nK), ptr(x), i64(nx),
+                                 ptr(prm), ptr(zi), i64(T), i64(M), ptr(lam), ptr(K_ts),
+                                 ptr(slow)))
+    return K_ts, lam, slow
+
+
+class HistSim:
+    """Device-resident histogram simulation: grids, the M shock paths and the distributions stay
+    in HBM across calls.  zi_paths (T, M) host array in {0, 1}; lam0 (M, 2, nx) or (2, nx).
+    `lam` persists across calls like PanelSim's population; set_lam restarts it."""
+
+    def __init__(self, k_grid, K_grid, x_grid, zi_paths, lam0, params, device="cuda"):
+        import torch
+        dev = torch.device(device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.k_grid = torch.as_tensor(np.ascontiguousarray(k_grid, np.float64), **f64)
+        self.K_grid = torch.as_tensor(np.ascontiguousarray(K_grid, np.float64), **f64)
+        self.x_grid = torch.as_tensor(np.ascontiguousarray(x_grid, np.float64), **f64)
+        zi = np.asarray(zi_paths)
+        zi = zi[:, None] if zi.ndim == 1 else zi
+        if not np.all((zi == 0) | (zi == 1)):
+            raise ValueError("zi_paths must hold 0 (good) or 1 (bad)")
+        self.T, self.M = zi.shape
+        self.nx = self.x_grid.numel()
+        self.zi = torch.as_tensor(np.ascontiguousarray(zi.T.astype(np.int8)), device=dev)
+        self.params = np.ascontiguousarray(params, np.float64)
+        if self.params.size != 13:
+            raise ValueError("params must hold the 13 KS doubles")
+        self.lam = torch.empty((self.M, 2, self.nx), **f64)
+        self.set_lam(lam0)
+        self.K_ts = torch.empty((self.M, self.T), **f64)
+        self.slow = torch.zeros(self.M, dtype=torch.int64, device=dev)
+
+    def set_lam(self, lam0):
+        import torch
+        lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (self.M, 2, self.nx)))
+        self.lam.copy_(torch.as_tensor(lam))
+
+    def __call__(self, k_opt, stream=None):
+        """One run with policy k_opt (device [S][K][k] = k x K x S column-major); returns K_ts
+        (device [M][T]); self.lam holds the last period's distribution, self.slow the counts."""
+        nS, nK, nk = k_opt.shape
+        if nS != 4 or nK != self.K_grid.numel() or nk != self.k_grid.numel():
+            raise ValueError("k_opt must be [4][numel(K_grid)][numel(k_grid)]")
+        check(lib().ks_simulate_hist_dev(i64(nk), i64(nK), ptr(self.k_grid), ptr(self.K_grid),
+                                         ptr(k_opt), ptr(self.x_grid), i64(self.nx),
+                                         ptr(self.params), ptr(self.zi), i64(self.T),
+                                         i64(self.M), ptr(self.lam), ptr(self.K_ts),
+                                         ptr(self.slow), stream_handle(stream)))
+        return self.K_ts
+
+
 # ------------------------------------------------------------------ ALM loop (host)
 
 
@@ -124,16 +247,57 @@ def alm_regress(K_ts, zi_shock, T_discard=100):
     return B, R2[0], R2[1]
 
 
+def alm_regress_paths(K_ts, zi, T_discard=100):
+    """The regression of :252-285 pooled over M shock paths: K_ts and zi are (T, M); the
+    observations (t, m), t = T_discard..T-1, are stacked path after path.  For M = 1 this is
+    alm_regress.  Returns (B_new, R2_good, R2_bad)."""
+    K_ts = np.asarray(K_ts, np.float64)
+    zi = np.asarray(zi)
+    if K_ts.ndim == 1:
+        K_ts, zi = K_ts[:, None], zi.reshape(-1, 1)
+    T, M = K_ts.shape
+    ts = np.arange(T_discard - 1, T - 1)
+    B = np.zeros(4)
+    R2 = [0.0, 0.0]
+    for g in (0, 1):
+        lk, lkn = [], []
+        for m in range(M):
+            sel = ts[zi[ts, m] == g]
+            lk.append(np.log(K_ts[sel, m]))
+            lkn.append(np.log(K_ts[sel + 1, m]))
+        lk, Y = np.concatenate(lk), np.concatenate(lkn)
+        if lk.size == 0:
+            continue
+        X = np.stack([np.ones(lk.size), lk], 1)
+        Q, R = np.linalg.qr(X)
+        b = np.linalg.solve(R, Q.T @ Y)
+        B[2 * g:2 * g + 2] = b
+        res = Y - X @ b
+        R2[g] = 1 - np.sum(res ** 2) / np.sum((Y - Y.mean()) ** 2)
+    return B, R2[0], R2[1]
+
+
 def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B=100, tol_B=1e-6,
                       update_B=0.3, howard_steps=50, tol_vfi=1e-6, max_vfi=10000, T_discard=100,
-                      uniforms=None, n_devices=1, log=None):
+                      uniforms=None, n_devices=1, log=None, simulate="panel", n_paths=1,
+                      nx=1000):
     """Krusell_Smith_VFI.m:4-296 end to end on the GPU kernels: shocks (F3), then per ALM
     iteration the VFI solve (A6/A7), the panel simulation (F2) and the host regression/update.
-    Returns dict(B, B_history, R2, K_ts, value, k_opt, vfi_iters)."""
+    Returns dict(B, B_history, R2, K_ts, value, k_opt, vfi_iters).
+    simulate="histogram": the capital path comes from the histogram simulation (HistSim) on
+    n_paths shock paths over an nx-point grid instead of the agent panel, and the regression is
+    pooled over the paths (alm_regress_paths); K_ts and zi are then (T, n_paths).  `uniforms`
+    then holds n_paths * (T - 1) aggregate draws."""
     from . import calibration
     from .ks import ks_params, ks_vfi_solve
+    if simulate not in ("panel", "histogram"):
+        raise ValueError(f'simulate must be "panel" or "histogram", got {simulate!r}')
     prm = ks_params()
     kg, Kg, P, V0 = calibration.krusell_smith(k_size=k_size, K_size=K_size)
+    if simulate == "histogram":
+        return _krusell_smith_vfi_hist(prm, kg, Kg, P, V0, T, max_iter_B, tol_B, update_B,
+                                       howard_steps, tol_vfi, max_vfi, T_discard, uniforms,
+                                       n_devices, log, n_paths, nx)
     U = matlab_rand(shock_draws(T, population)) if uniforms is None else uniforms
     zi, eps = ks_shocks(T, population, U, prm)
     value = V0
@@ -158,3 +322,52 @@ def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
         B = update_B * B_new + (1 - update_B) * B                                # :295
     return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, value=value, k_opt=k_opt,
                 vfi_iters=vfi_iters, zi=zi)
+
+
+def _krusell_smith_vfi_hist(prm, kg, Kg, P, V0, T, max_iter_B, tol_B, update_B, howard_steps,
+                            tol_vfi, max_vfi, T_discard, uniforms, n_devices, log, n_paths, nx):
+    """krusell_smith_vfi's loop with the histogram simulation in place of the panel.  Between
+    ALM iterations the capital marginal of the last distribution is carried and re-split
+    (1 - ug, ug) over employment — the analogue of k_population persisting (:101) while
+    epsi_shock restarts at its first row."""
+    import torch
+    from .ks import ks_vfi_solve
+    k_size, K_size = kg.size, Kg.size
+    ug = float(prm[5])
+    U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
+    zi = zi_paths(T, n_paths, U, prm)
+    x = hist_grid(nx, float(prm[3]), float(prm[4]))
+    sim = HistSim(kg, Kg, x, zi, hist_start(x, Kg[0], ug), prm)
+    value = V0
+    k_opt = 0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2)    # :97
+    B = np.array([0.0, 1.0, 0.0, 1.0])                                          # :99
+    hist, R2, K_ts, vfi_iters, slow = [], (0.0, 0.0), None, [], None
+    for it in range(max_iter_B):
+        R = ks_vfi_solve(value, k_opt, kg, Kg, B, P, prm, howard_steps=howard_steps, tol=tol_vfi,
+                         max_vfi=max_vfi, n_devices=n_devices)
+        value, k_opt = R["value"], R["k_opt"]
+        vfi_iters.append(R["iters"])
+        ko_dev = torch.as_tensor(np.ascontiguousarray(k_opt.transpose(2, 1, 0)),
+                                 device=sim.lam.device)
+        K_ts = sim(ko_dev).cpu().numpy().T
+        slow = sim.slow.cpu().numpy()
+        lam = sim.lam.cpu().numpy()
+        sim.set_lam(hist_carry(lam, ug))
+        B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
+        R2 = (r2g, r2b)
+        diff_B = float(np.max(np.abs(B_new - B)))                              # :286
+        hist.append(B_new.copy())
+        if log:
+            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
+        if diff_B < tol_B:
+            break
+        B = update_B * B_new + (1 - update_B) * B                                # :295
+    return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, value=value, k_opt=k_opt,
+                vfi_iters=vfi_iters, zi=zi, slow_periods=slow, x_grid=x)
+
+
+def hist_carry(lam, ug):
+    """The start of the next ALM iteration from the last distributions lam (M, 2, nx): the
+    capital marginal lam[:, 0] + lam[:, 1], re-split (1 - ug, ug) over employment."""
+    marg = lam[:, 0, :] + lam[:, 1, :]
+    return np.stack([(1 - ug) * marg, ug * marg], 1)

@@ -288,6 +288,23 @@ int ks_simulate_capital(const double* k_opt, const double* k_grid, const double*
                         const double* epsi_shock, int64_t T, int64_t population,
                         double* k_population, double* K_ts);
 
+/* F2 histogram — the non-stochastic simulation (Young 2010) of the capital path beside the
+ * agent panel of ks_simulate_capital (new; no reference counterpart).  A distribution lam over
+ * (employment, node of x_grid) is pushed through M aggregate shock paths with the period's
+ * policy; K_ts(t, m) = sum(lam .* x) is its first moment (not normalised).  k_opt k x K x 4;
+ * x_grid nx (strictly increasing, nx >= 2); params: the 13 KS doubles; zi_shock T x M
+ * column-major (0 good / 1 bad); lam nx x 2 x M column-major, in/out (column 1 employed,
+ * 2 unemployed; out: the distribution of period T); K_ts out T x M; slow_periods (nullable,
+ * M): periods whose lottery keys were not monotone and were summed by the ordered scan.
+ * The recursion and both summation orders are stated in csrc/ks_hist_kernels.hip and DESIGN.md
+ * §5.  One launch: path m is one workgroup, so a path's state must fit one CU's LDS
+ * (8*(8*nx + K_size + 8) + 4*(5*nx + 4) <= 160 KiB, else AIY_BAD_SHAPE); 1 <= M <= 65,535,
+ * T >= 2. */
+int ks_simulate_hist(const double* k_opt, const double* k_grid, const double* K_grid, int64_t nk,
+                     int64_t nK, const double* x_grid, int64_t nx, const double* params,
+                     const double* zi_shock, int64_t T, int64_t M, double* lam, double* K_ts,
+                     int64_t* slow_periods);
+
 /* ======================================================================================
  * Device tier: [N][Na] (z-major) arrays in HBM, async on `stream` (hipStream_t).
  * A workspace holds the per-shape scratch (EV/D tables, init/partial buffers, events).
@@ -666,6 +683,15 @@ int ks_simulate_capital_dev(int64_t nk, int64_t nK, const double* k_grid, const 
                             const double* k_opt, int64_t T, int64_t population,
                             const int8_t* zi, const int8_t* eps, double* k_population,
                             double* K_ts, void* scratch, void* stream);
+
+/* ---- F2 histogram device tier.  Grids, k_opt (k x K x 4 column-major), zi (int8 [M][T]), lam
+ * ([M][2][nx], in/out) and K_ts ([M][T], out) and slow_periods (int64 [M], nullable) in HBM;
+ * params on the host.  Shapes and params are validated before the launch; the contents of
+ * device arrays are the caller's (a zi code other than 0 counts as 1). */
+int ks_simulate_hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
+                         const double* k_opt, const double* x_grid, int64_t nx,
+                         const double* params, const int8_t* zi, int64_t T, int64_t M,
+                         double* lam, double* K_ts, int64_t* slow_periods, void* stream);
 
 #ifdef __cplusplus
 }
