@@ -64,11 +64,128 @@ static void ks_egm_pairs(const double* prm, const double* K_grid, const double* 
     }
 }
 
+// ---- the batched solve: C economies, one workgroup each (ks_egm_solve_batch_kernel)
+
+// what both tiers check on their host arguments, before any device work
+static int check_egm_batch(int64_t C, const double* K_grid, int64_t nk, int64_t nK,
+                           int64_t max_iter) {
+    if (C < 1 || C > kEgmBatchMaxCand) return fail(AIY_BAD_SHAPE, "need 1 <= C <= 65,535 candidates");
+    if (nk < 3 || nK < 1 || nk > (1 << 20))
+        return fail(AIY_BAD_SHAPE, "need k_size >= 3 and K_size >= 1");
+    if (max_iter < 1 || max_iter > 2147483647) return fail(AIY_BAD_ARG, "max_iter in [1, 2^31)");
+    if (!ks_egm_fits((int)nk, (int)nK))
+        return fail(AIY_BAD_SHAPE, "k_size x K_size too large for the one-workgroup EGM solve");
+    for (int64_t c = 0; c < C; ++c)
+        for (int64_t q = 0; q < nK; ++q)
+            if (!(K_grid[c * nK + q] > 0) || !std::isfinite(K_grid[c * nK + q]))
+                return fail(AIY_NON_FINITE, "K_grid must be positive and finite (candidate %lld)",
+                            (long long)(c + 1));
+    return AIY_OK;
+}
+
+// device scratch of one call: the candidates' KsEgmCand blocks, then their pair tables
+static size_t egm_batch_scratch(int64_t C, int64_t nK) {
+    return (size_t)C * (sizeof(KsEgmCand) + 4 * (size_t)nK * sizeof(KsEgmPair));
+}
+
+// Builds the candidates' tables on the host (libm, as ks_egm_pairs), uploads them into `scratch`
+// and enqueues the one launch.  The upload is ordered on `st` behind whatever still reads
+// `scratch`, and the call waits for it before the host table dies; the solve itself is left
+// running on `st`.
+static int egm_batch_dev(int64_t C, double* k_opt, const double* k_grid, const double* K_grid,
+                         const double* B, const double* P, const double* params, int64_t nk,
+                         int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
+                         int32_t* status, void* scratch, hipStream_t st) {
+    std::vector<KsEgmCand> cand(C);
+    std::vector<KsEgmPair> pairs((size_t)C * 4 * nK), one;
+    for (int64_t c = 0; c < C; ++c) {
+        const double* prm = params + 13 * c;
+        ks_egm_pairs(prm, K_grid + c * nK, B + 4 * c, (int)nK, one);
+        std::copy(one.begin(), one.end(), pairs.begin() + (size_t)c * 4 * nK);
+        for (int i = 0; i < 4; ++i)
+            for (int m = 0; m < 4; ++m) cand[c].P[i * 4 + m] = P[16 * c + i + m * 4];
+        cand[c].beta = prm[0];
+        cand[c].k_min = prm[3];
+        cand[c].k_max = prm[4];
+    }
+    KsEgmCand* dcand = (KsEgmCand*)scratch;
+    KsEgmPair* dpairs = (KsEgmPair*)(dcand + C);
+    AIY_HIP(hipMemcpyAsync(dcand, cand.data(), cand.size() * sizeof(KsEgmCand),
+                           hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemcpyAsync(dpairs, pairs.data(), pairs.size() * sizeof(KsEgmPair),
+                           hipMemcpyHostToDevice, st));
+    AIY_HIP(hipStreamSynchronize(st));
+    KsEgmBatchArgs A{};
+    A.nk = (int)nk;
+    A.nK = (int)nK;
+    A.max_iter = (int)max_iter;
+    A.C = (int)C;
+    A.k_grid = k_grid;
+    A.cand = dcand;
+    A.pairs = dpairs;
+    A.tol = tol;
+    A.k_opt = k_opt;
+    A.iters = iters;
+    A.diff = diff;
+    A.status = status;
+    return launch_ks_egm_solve_batch(A, st);
+}
+
 }  // namespace aiy
 
 using namespace aiy;
 
 extern "C" {
+
+int64_t ks_egm_batch_scratch_bytes(int64_t C, int64_t nK) {
+    return (C < 1 || nK < 1) ? 0 : (int64_t)egm_batch_scratch(C, nK);
+}
+
+int ks_egm_solve_batch_dev(int64_t C, double* k_opt, const double* k_grid, const double* K_grid,
+                           const double* B, const double* P, const double* params, int64_t nk,
+                           int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
+                           int32_t* status, void* scratch, void* stream) {
+    if (!k_opt || !k_grid || !K_grid || !B || !P || !params || !iters || !diff || !status ||
+        !scratch)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_egm_batch(C, K_grid, nk, nK, max_iter));
+    return egm_batch_dev(C, k_opt, k_grid, K_grid, B, P, params, nk, nK, tol, max_iter, iters,
+                         diff, status, scratch, (hipStream_t)stream);
+}
+
+int ks_egm_solve_batch(int64_t C, double* k_opt, const double* k_grid, const double* K_grid,
+                       const double* B, const double* P, const double* params, int64_t nk,
+                       int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
+                       int32_t* status) {
+    if (!k_opt || !k_grid || !K_grid || !B || !P || !params || !iters || !diff || !status)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_egm_batch(C, K_grid, nk, nK, max_iter));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
+    const size_t n = (size_t)C * nk * nK * 4;
+    double *dkg, *dk, *ddiff;
+    int64_t* dit;
+    int32_t* dst;
+    void* dscr;
+    AIY_TRY(c->buf("egmb_kg", nk * sizeof(double), (void**)&dkg));
+    AIY_TRY(c->buf("egmb_k", n * sizeof(double), (void**)&dk));
+    AIY_TRY(c->buf("egmb_iters", C * sizeof(int64_t), (void**)&dit));
+    AIY_TRY(c->buf("egmb_diff", C * sizeof(double), (void**)&ddiff));
+    AIY_TRY(c->buf("egmb_status", C * sizeof(int32_t), (void**)&dst));
+    AIY_TRY(c->buf("egmb_scratch", egm_batch_scratch(C, nK), &dscr));
+    AIY_HIP(hipMemcpyAsync(dkg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dk, k_opt, n * sizeof(double), hipMemcpyHostToDevice, c->st));
+    AIY_TRY(egm_batch_dev(C, dk, dkg, K_grid, B, P, params, nk, nK, tol, max_iter, dit, ddiff, dst,
+                          dscr, c->st));
+    AIY_HIP(hipMemcpyAsync(iters, dit, C * sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(diff, ddiff, C * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(status, dst, C * sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(k_opt, dk, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipStreamSynchronize(c->st));
+    return AIY_OK;
+}
 
 int ks_egm_solve(double* k_opt, const double* k_grid, const double* K_grid, const double* B,
                  const double* P, const double* params, int64_t nk, int64_t nK, double tol,

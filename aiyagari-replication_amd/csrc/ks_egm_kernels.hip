@@ -27,8 +27,10 @@ __device__ __forceinline__ bool sort_gt(double a, double b) {
     return (a != a) ? (b == b) : (b == b && a > b);
 }
 
-__global__ __launch_bounds__(kEgmThreads) void ks_egm_solve_kernel(KsEgmArgs A, double* kopt_io,
-                                                                   KsEgmOut* out) {
+// The whole solve of one economy by the calling workgroup: k_opt staged in LDS, the sweeps, the
+// stop rule, k_opt written back.  Every thread returns the same (it, diff, status).
+__device__ __forceinline__ void ks_egm_solve_body(const KsEgmArgs& A, double* kopt_io, int& it_out,
+                                                  double& diff_out, int& status_out) {
     extern __shared__ double lds[];
     const int nk = A.nk, nK = A.nK, n_all = nk * nK * 4;
     double* kg = lds;
@@ -131,10 +133,49 @@ __global__ __launch_bounds__(kEgmThreads) void ks_egm_solve_kernel(KsEgmArgs A, 
     }
     if (it > A.max_iter) it = A.max_iter;
     for (int q = tid; q < n_all; q += blockDim.x) kopt_io[q] = K[q];
-    if (tid == 0) {
+    it_out = it;
+    diff_out = diff;
+    status_out = status;
+}
+
+__global__ __launch_bounds__(kEgmThreads) void ks_egm_solve_kernel(KsEgmArgs A, double* kopt_io,
+                                                                   KsEgmOut* out) {
+    int it, status;
+    double diff;
+    ks_egm_solve_body(A, kopt_io, it, diff, status);
+    if (threadIdx.x == 0) {
         out->iters = it;
         out->diff = diff;
         out->status = status;
+    }
+}
+
+// A8 batch — C independent economies, workgroup c running ks_egm_solve_body on candidate c's
+// k_opt slice with its own pair table, P, beta, k_min and k_max (KsEgmCand); k_grid, the sizes,
+// tol and max_iter are shared.  The candidates share nothing that is written: no workgroup waits
+// for or signals another, and a candidate that meets fewer than two valid EGM points sets its
+// own status and leaves.  The grid is exactly C workgroups.
+__global__ __launch_bounds__(kEgmThreads) void ks_egm_solve_batch_kernel(KsEgmBatchArgs B) {
+    const int c = blockIdx.x;
+    const KsEgmCand& cd = B.cand[c];
+    KsEgmArgs A;
+    A.nk = B.nk;
+    A.nK = B.nK;
+    A.max_iter = B.max_iter;
+    A.k_grid = B.k_grid;
+    A.P = cd.P;
+    A.pairs = B.pairs + (size_t)c * 4 * B.nK;
+    A.beta = cd.beta;
+    A.k_min = cd.k_min;
+    A.k_max = cd.k_max;
+    A.tol = B.tol;
+    int it, status;
+    double diff;
+    ks_egm_solve_body(A, B.k_opt + (size_t)c * 4 * B.nK * B.nk, it, diff, status);
+    if (threadIdx.x == 0) {
+        B.iters[c] = it;
+        B.diff[c] = diff;
+        B.status[c] = status;
     }
 }
 
@@ -239,6 +280,18 @@ bool ks_egm_fits(int nk, int nK) { return ks_egm_lds_bytes(nk, nK) <= 150 * 1024
 
 int launch_ks_egm_solve(const KsEgmArgs& A, double* kopt, KsEgmOut* out, hipStream_t st) {
     ks_egm_solve_kernel<<<1, kEgmThreads, ks_egm_lds_bytes(A.nk, A.nK), st>>>(A, kopt, out);
+    AIY_HIP(hipGetLastError());
+    return AIY_OK;
+}
+
+int launch_ks_egm_solve_batch(const KsEgmBatchArgs& B, hipStream_t st) {
+    if (B.C < 1 || B.C > kEgmBatchMaxCand || !ks_egm_fits(B.nk, B.nK))
+        return fail(AIY_BAD_SHAPE, "batched EGM solve: need 1 <= C <= 65,535 and a candidate's "
+                                   "k_opt inside the one-workgroup LDS rule");
+    const size_t lds = ks_egm_lds_bytes(B.nk, B.nK);
+    if (lds > 64 * 1024)  // dynamic LDS past 64 KiB needs the attribute
+        AIY_TRY((raise_dynamic_lds<ks_egm_solve_batch_kernel>(150 * 1024)));
+    ks_egm_solve_batch_kernel<<<B.C, kEgmThreads, lds, st>>>(B);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }

@@ -44,6 +44,12 @@ struct HistArgs {
     double* lam;             // [M][2][nx] in/out
     double* K_ts;            // [M][T] out
     int64_t* slow;           // [M] periods on the ordered-scan path (nullable)
+    // One policy per path (ks_simulate_hist_multi): path m runs candidate c = pol[m] — k_opt
+    // block c of [C][4][nK][nk], K_grid row c of [C][nK] and thr_g + 8·c (the candidate's own
+    // employment table, in global memory: the LDS map does not grow).  pol = nullptr: every path
+    // runs the one k_opt / K_grid / thr above.
+    const int32_t* pol;      // [M], each in [0, C)
+    const double* thr_g;     // [C][8]
 };
 int launch_ks_hist(const HistArgs& A, hipStream_t st);
 

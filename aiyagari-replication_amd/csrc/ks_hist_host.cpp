@@ -63,11 +63,143 @@ int hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
     return launch_ks_hist(A, st);
 }
 
+// ---- one policy per path.  Device scratch of a call: thr [C][8] doubles, then pol [M] int32.
+static size_t hist_multi_scratch(int64_t C, int64_t M) {
+    return sizeof(double) * 8 * (size_t)C + sizeof(int32_t) * (size_t)M;
+}
+
+static int check_hist_multi(int64_t C, const double* params, const int32_t* pol, int64_t M) {
+    if (C < 1 || C > kHistMaxPaths) return fail(AIY_BAD_SHAPE, "need 1 <= C <= 65,535 candidates");
+    for (int64_t c = 0; c < C; ++c) AIY_TRY(check_hist_params(params + 13 * c));
+    for (int64_t m = 0; m < M; ++m)
+        if (pol[m] < 0 || pol[m] >= C)
+            return fail(AIY_BAD_ARG, "policy_of_path(%lld) = %d is outside [0, C)",
+                        (long long)(m + 1), (int)pol[m]);
+    return AIY_OK;
+}
+
+// k_grid, K_grid [C][nK], k_opt [C][4][nK][nk], x_grid, zi, lam, K_ts, slow and scratch on the
+// device; params [C][13] and pol [M] on the host (validated by the caller).  The tables are
+// uploaded on `st` and the call waits for that copy before they die; the launch is left running.
+static int hist_multi_dev(int64_t C, int64_t nk, int64_t nK, const double* k_grid,
+                          const double* K_grid, const double* k_opt, const double* x_grid,
+                          int64_t nx, const double* params, const int32_t* pol, const int8_t* zi,
+                          int64_t T, int64_t M, double* lam, double* K_ts, int64_t* slow,
+                          void* scratch, hipStream_t st) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(AIY_NO_DEVICE, "no HIP device visible");
+    std::vector<double> thr(8 * (size_t)C);
+    for (int64_t c = 0; c < C; ++c) {
+        ShockArgs S{};
+        shock_probs(params[13 * c + 5], params[13 * c + 6], S);
+        for (int q = 0; q < 8; ++q) thr[8 * c + q] = S.thr[q];
+    }
+    double* dthr = (double*)scratch;
+    int32_t* dpol = (int32_t*)(dthr + 8 * C);
+    AIY_HIP(hipMemcpyAsync(dthr, thr.data(), sizeof(double) * thr.size(), hipMemcpyHostToDevice, st));
+    AIY_HIP(hipMemcpyAsync(dpol, pol, sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
+    AIY_HIP(hipStreamSynchronize(st));
+    HistArgs A{};
+    A.nx = (int)nx;
+    A.nk = (int)nk;
+    A.nK = (int)nK;
+    A.T = (int)T;
+    A.M = (int)M;
+    A.k_grid = k_grid;
+    A.K_grid = K_grid;
+    A.x = x_grid;
+    A.k_opt = k_opt;
+    A.zi = zi;
+    A.lam = lam;
+    A.K_ts = K_ts;
+    A.slow = slow;
+    A.pol = dpol;
+    A.thr_g = dthr;
+    return launch_ks_hist(A, st);
+}
+
 }  // namespace aiy
 
 using namespace aiy;
 
 extern "C" {
+
+int64_t ks_hist_multi_scratch_bytes(int64_t C, int64_t M) {
+    return (C < 1 || M < 1) ? 0 : (int64_t)hist_multi_scratch(C, M);
+}
+
+int ks_simulate_hist_multi_dev(int64_t C, int64_t nk, int64_t nK, const double* k_grid,
+                               const double* K_grid, const double* k_opt, const double* x_grid,
+                               int64_t nx, const double* params, const int32_t* policy_of_path,
+                               const int8_t* zi, int64_t T, int64_t M, double* lam, double* K_ts,
+                               int64_t* slow_periods, void* scratch, void* stream) {
+    if (!k_grid || !K_grid || !k_opt || !x_grid || !params || !policy_of_path || !zi || !lam ||
+        !K_ts || !scratch)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_hist_shape(nk, nK, nx, T, M));
+    AIY_TRY(check_hist_multi(C, params, policy_of_path, M));
+    return hist_multi_dev(C, nk, nK, k_grid, K_grid, k_opt, x_grid, nx, params, policy_of_path, zi,
+                          T, M, lam, K_ts, slow_periods, scratch, (hipStream_t)stream);
+}
+
+int ks_simulate_hist_multi(int64_t C, const double* k_opt, const double* k_grid,
+                           const double* K_grid, int64_t nk, int64_t nK, const double* x_grid,
+                           int64_t nx, const double* params, const int32_t* policy_of_path,
+                           const double* zi_shock, int64_t T, int64_t M, double* lam,
+                           double* K_ts, int64_t* slow_periods) {
+    if (!k_opt || !k_grid || !K_grid || !x_grid || !params || !policy_of_path || !zi_shock ||
+        !lam || !K_ts)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_hist_shape(nk, nK, nx, T, M));
+    AIY_TRY(check_hist_multi(C, params, policy_of_path, M));
+    AIY_TRY(check_grid_strict(k_grid, nk));  // all three are interpolated
+    for (int64_t c = 0; c < C; ++c) AIY_TRY(check_grid_strict(K_grid + c * nK, nK));
+    AIY_TRY(check_grid_strict(x_grid, nx));
+    const size_t nko = (size_t)C * nk * nK * 4, nl = (size_t)2 * nx * M, nz = (size_t)T * M;
+    for (size_t q = 0; q < nko; ++q)
+        if (!std::isfinite(k_opt[q])) return fail(AIY_NON_FINITE, "non-finite k_opt");
+    for (size_t q = 0; q < nl; ++q)
+        if (!std::isfinite(lam[q])) return fail(AIY_NON_FINITE, "non-finite lam");
+    std::vector<int8_t> hz(nz);
+    for (size_t q = 0; q < nz; ++q) {
+        if (zi_shock[q] != 0 && zi_shock[q] != 1)
+            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
+        hz[q] = (int8_t)zi_shock[q];
+    }
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
+    double *dko, *dkg, *dKg, *dx, *dlam, *dKts;
+    int64_t* dslow;
+    int8_t* dz;
+    void* dscr;
+    AIY_TRY(c->buf("kshm_kopt", sizeof(double) * nko, (void**)&dko));
+    AIY_TRY(c->buf("kshm_kg", sizeof(double) * nk, (void**)&dkg));
+    AIY_TRY(c->buf("kshm_Kg", sizeof(double) * C * nK, (void**)&dKg));
+    AIY_TRY(c->buf("kshm_x", sizeof(double) * nx, (void**)&dx));
+    AIY_TRY(c->buf("kshm_lam", sizeof(double) * nl, (void**)&dlam));
+    AIY_TRY(c->buf("kshm_Kts", sizeof(double) * nz, (void**)&dKts));
+    AIY_TRY(c->buf("kshm_slow", sizeof(int64_t) * M, (void**)&dslow));
+    AIY_TRY(c->buf("kshm_zi", nz, (void**)&dz));
+    AIY_TRY(c->buf("kshm_scratch", hist_multi_scratch(C, M), &dscr));
+    AIY_HIP(hipMemcpyAsync(dko, k_opt, sizeof(double) * nko, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dkg, k_grid, sizeof(double) * nk, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dKg, K_grid, sizeof(double) * C * nK, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dx, x_grid, sizeof(double) * nx, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dlam, lam, sizeof(double) * nl, hipMemcpyHostToDevice, c->st));
+    AIY_HIP(hipMemcpyAsync(dz, hz.data(), nz, hipMemcpyHostToDevice, c->st));
+    AIY_TRY(hist_multi_dev(C, nk, nK, dkg, dKg, dko, dx, nx, params, policy_of_path, dz, T, M,
+                           dlam, dKts, dslow, dscr, c->st));
+    AIY_HIP(hipMemcpyAsync(lam, dlam, sizeof(double) * nl, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipMemcpyAsync(K_ts, dKts, sizeof(double) * nz, hipMemcpyDeviceToHost, c->st));
+    std::vector<int64_t> hs(M);
+    AIY_HIP(hipMemcpyAsync(hs.data(), dslow, sizeof(int64_t) * M, hipMemcpyDeviceToHost, c->st));
+    AIY_HIP(hipStreamSynchronize(c->st));
+    if (slow_periods)
+        for (int64_t m = 0; m < M; ++m) slow_periods[m] = hs[m];
+    return AIY_OK;
+}
 
 int ks_simulate_hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
                          const double* k_opt, const double* x_grid, int64_t nx,

@@ -80,7 +80,10 @@ __device__ __forceinline__ void hist_moment(const double* s_lam, const double* s
     }
 }
 
-template <bool KLDS>
+// MULTI: path m runs its own candidate c = A.pol[m] — k_opt block c, K_grid row c and the
+// employment table A.thr_g + 8·c (read from global memory in phase 5); everything else, the
+// LDS map included, is the single-policy kernel's.
+template <bool KLDS, bool MULTI>
 __global__ __launch_bounds__(1024) void ks_hist_sim_kernel(HistArgs A) {
     extern __shared__ __align__(16) unsigned char ks_hist_lds[];
     const int m = blockIdx.x;  // (the grid is exactly M workgroups)
@@ -103,6 +106,10 @@ __global__ __launch_bounds__(1024) void ks_hist_sim_kernel(HistArgs A) {
     double* __restrict__ lam_g = A.lam + (size_t)m * n;
     const int8_t* __restrict__ zi = A.zi + (size_t)m * T;
     double* __restrict__ Kts = A.K_ts + (size_t)m * T;
+    const int cand = MULTI ? A.pol[m] : 0;
+    const double* __restrict__ ko_g = A.k_opt + (size_t)cand * 4 * nK * nk;
+    const double* __restrict__ Kg_g = A.K_grid + (size_t)cand * nK;
+    const double* __restrict__ thr_c = MULTI ? A.thr_g + 8 * (size_t)cand : nullptr;
 
     for (int j = tid; j < nx; j += nthr) {
         const double xj = A.x[j];
@@ -111,12 +118,12 @@ __global__ __launch_bounds__(1024) void ks_hist_sim_kernel(HistArgs A) {
         s_ik[j] = ik;
         s_tk[j] = (xj - kg[ik]) / (kg[ik + 1] - kg[ik]);
     }
-    for (int q = tid; q < nK; q += nthr) s_Kg[q] = A.K_grid[q];
+    for (int q = tid; q < nK; q += nthr) s_Kg[q] = Kg_g[q];
     if (tid < 2) s_vote[tid] = 0;
     for (int f = tid; f < n; f += nthr) s_lam[f] = lam_g[f];
     if (KLDS)
-        for (int q = tid; q < 4 * nK * nk; q += nthr) s_ko[q] = A.k_opt[q];
-    const double* ko = KLDS ? s_ko : A.k_opt;
+        for (int q = tid; q < 4 * nK * nk; q += nthr) s_ko[q] = ko_g[q];
+    const double* ko = KLDS ? s_ko : ko_g;
     __syncthreads();
 
     const double x0 = s_x[0], xn = s_x[nx - 1];
@@ -214,7 +221,8 @@ __global__ __launch_bounds__(1024) void ks_hist_sim_kernel(HistArgs A) {
         }
         __syncthreads();
         {  // phase 5
-            const double p0 = A.thr[(zn * 2 + zt) * 2 + 0], p1 = A.thr[(zn * 2 + zt) * 2 + 1];
+            const int ti = (zn * 2 + zt) * 2;
+            const double p0 = MULTI ? thr_c[ti] : A.thr[ti], p1 = MULTI ? thr_c[ti + 1] : A.thr[ti + 1];
             int e = e0, k = j0;
             for (int f = tid; f < n; f += nthr) {
                 const double a0 = e == 0 ? p0 : 1 - p0, a1 = e == 0 ? p1 : 1 - p1;
@@ -250,15 +258,18 @@ int launch_ks_hist(const HistArgs& A, hipStream_t st) {
     const bool klds = ks_hist_kopt_in_lds(A.nx, A.nk, A.nK);
     const size_t lds = ks_hist_lds_bytes(A.nx, A.nk, A.nK, klds);
     const int nthr = std::min(1024, std::max(kHistFold, (2 * A.nx + 63) & ~63));
-    if (klds) {
-        if (lds > 64 * 1024)  // dynamic LDS past 64 KiB needs the attribute
-            AIY_TRY((raise_dynamic_lds<ks_hist_sim_kernel<true>>((int)kHistMaxLds)));
-        ks_hist_sim_kernel<true><<<A.M, nthr, lds, st>>>(A);
-    } else {
-        if (lds > 64 * 1024)
-            AIY_TRY((raise_dynamic_lds<ks_hist_sim_kernel<false>>((int)kHistMaxLds)));
-        ks_hist_sim_kernel<false><<<A.M, nthr, lds, st>>>(A);
-    }
+    const bool multi = A.pol != nullptr;
+#define AIY_HIST_LAUNCH(KLDS_, MULTI_)                                                          \
+    do {                                                                                        \
+        if (lds > 64 * 1024) /* dynamic LDS past 64 KiB needs the attribute */                  \
+            AIY_TRY((raise_dynamic_lds<ks_hist_sim_kernel<KLDS_, MULTI_>>((int)kHistMaxLds)));  \
+        ks_hist_sim_kernel<KLDS_, MULTI_><<<A.M, nthr, lds, st>>>(A);                           \
+    } while (0)
+    if (klds && multi) AIY_HIST_LAUNCH(true, true);
+    else if (klds) AIY_HIST_LAUNCH(true, false);
+    else if (multi) AIY_HIST_LAUNCH(false, true);
+    else AIY_HIST_LAUNCH(false, false);
+#undef AIY_HIST_LAUNCH
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }

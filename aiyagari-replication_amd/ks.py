@@ -84,3 +84,84 @@ def ks_egm_solve(k_opt, k_grid, K_grid, B, P, params, tol=1e-6, max_iter=10000, 
     check(fn(ptr(ko), ptr(kg), ptr(Kg), ptr(B), ptr(P), ptr(prm), i64(nk), i64(nK), d(tol),
              i64(max_iter), C.byref(it), C.byref(diff)))
     return dict(k_opt=ko, iters=it.value, diff=diff.value)
+
+
+def _per_candidate(x, C_, tail, name):
+    """x as a C-contiguous (C, *tail) float64 array; a single candidate's block broadcasts."""
+    a = np.asarray(x, np.float64)
+    if a.shape == tuple(tail):
+        a = np.broadcast_to(a, (C_,) + tuple(tail))
+    if a.shape != (C_,) + tuple(tail):
+        raise ValueError(f"{name} must be {tuple(tail)} or ({C_},) + {tuple(tail)}, "
+                         f"got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def egm_batch_inputs(C_, nK, K_grid, B, P, params):
+    """The candidate-major host arrays of the batched solve: K_grid (C, nK), B (C, 4), P (C, 4, 4)
+    with each block in MATLAB's column-major order, params (C, 13).  Shared inputs broadcast."""
+    Kg = _per_candidate(K_grid, C_, (nK,), "K_grid")
+    Bc = _per_candidate(B, C_, (4,), "B")
+    Pc = _per_candidate(P, C_, (4, 4), "P")
+    Pc = np.ascontiguousarray(Pc.transpose(0, 2, 1))   # each block column-major
+    prm = _per_candidate(params, C_, (13,), "params")
+    return Kg, Bc, Pc, prm
+
+
+def ks_egm_solve_batch(k_opt, k_grid, K_grid, B, P, params, tol=1e-6, max_iter=10000):
+    """A8 at C candidate economies in one launch (ks_egm_solve_batch): k_opt (C, nk, nK, 4),
+    K_grid (C, nK), B (C, 4), P (C, 4, 4), params (C, 13); a shared K_grid, B, P or params (one
+    candidate's shape) broadcasts.  Returns dict(k_opt (C, nk, nK, 4), iters (C,), diff (C,),
+    status (C,)): status 1 marks a candidate that met fewer than two valid EGM points (its k_opt
+    is unspecified); every other candidate equals its own ks_egm_solve bit for bit."""
+    ko = np.asarray(k_opt, np.float64)
+    if ko.ndim != 4 or ko.shape[3] != 4:
+        raise ValueError("k_opt must be (C, k_size, K_size, 4)")
+    C_, nk, nK, _ = ko.shape
+    kg = np.ascontiguousarray(k_grid, np.float64)
+    if kg.shape != (nk,):
+        raise ValueError("k_opt must be (C, numel(k_grid), K_size, 4)")
+    Kg, Bc, Pc, prm = egm_batch_inputs(C_, nK, K_grid, B, P, params)
+    # candidate-major, each block k x K x 4 column-major = [4][nK][nk] row-major
+    kd = np.ascontiguousarray(ko.transpose(0, 3, 2, 1))
+    iters = np.zeros(C_, np.int64)
+    diff = np.zeros(C_)
+    status = np.zeros(C_, np.int32)
+    check(lib().ks_egm_solve_batch(i64(C_), ptr(kd), ptr(kg), ptr(Kg), ptr(Bc), ptr(Pc), ptr(prm),
+                                   i64(nk), i64(nK), d(tol), i64(max_iter), ptr(iters), ptr(diff),
+                                   ptr(status)))
+    return dict(k_opt=kd.transpose(0, 3, 2, 1), iters=iters, diff=diff, status=status)
+
+
+def ks_egm_solve_batch_dev(k_opt, k_grid, K_grid, B, P, params, tol=1e-6, max_iter=10000,
+                           out=None, scratch=None, stream=None):
+    """Device tier of ks_egm_solve_batch: k_opt a device tensor [C][4][nK][nk] (in/out), k_grid a
+    device tensor; K_grid, B, P, params host arrays as in ks_egm_solve_batch.  `out` = (iters
+    int64, diff float64, status int32) device tensors [C] and `scratch` a device byte tensor of
+    ks_egm_batch_scratch_bytes(C, nK) are allocated when None.  Asynchronous on `stream` after the
+    table upload; returns (iters, diff, status, scratch)."""
+    import torch
+    from ._capi import stream_handle
+    C_, nS, nK, nk = k_opt.shape
+    if nS != 4 or k_grid.numel() != nk:
+        raise ValueError("k_opt must be [C][4][K_size][numel(k_grid)]")
+    if not k_opt.is_contiguous():
+        raise ValueError("k_opt must be a contiguous tensor")
+    Kg, Bc, Pc, prm = egm_batch_inputs(C_, nK, K_grid, B, P, params)
+    dev = k_opt.device
+    lib().ks_egm_batch_scratch_bytes.restype = C.c_int64
+    need = int(lib().ks_egm_batch_scratch_bytes(i64(C_), i64(nK)))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    if scratch.numel() < need:
+        raise ValueError(f"scratch holds {scratch.numel()} bytes, the call needs {need}")
+    if out is None:
+        out = (torch.zeros(C_, dtype=torch.int64, device=dev),
+               torch.zeros(C_, dtype=torch.float64, device=dev),
+               torch.zeros(C_, dtype=torch.int32, device=dev))
+    iters, diff, status = out
+    check(lib().ks_egm_solve_batch_dev(i64(C_), ptr(k_opt), ptr(k_grid), ptr(Kg), ptr(Bc), ptr(Pc),
+                                       ptr(prm), i64(nk), i64(nK), d(tol), i64(max_iter),
+                                       ptr(iters), ptr(diff), ptr(status), ptr(scratch),
+                                       stream_handle(stream)))
+    return iters, diff, status, scratch

@@ -221,6 +221,118 @@ class HistSim:
         return self.K_ts
 
 
+def _multi_shapes(k_opt, k_grid, K_grid, params, policy_of_path, M):
+    """Candidate-major host inputs of the one-policy-per-path simulation: k_opt (C, nk, nK, 4),
+    K_grid (C, nK) and params (C, 13) (one candidate's shape broadcasts), policy_of_path (M,)."""
+    from .ks import _per_candidate
+    ko = np.asarray(k_opt, np.float64)
+    if ko.ndim != 4 or ko.shape[3] != 4:
+        raise ValueError("k_opt must be (C, k_size, K_size, 4)")
+    C_, nk, nK, _ = ko.shape
+    if k_grid.size != nk:
+        raise ValueError("k_opt must be (C, numel(k_grid), K_size, 4)")
+    Kg = _per_candidate(K_grid, C_, (nK,), "K_grid")
+    prm = _per_candidate(params, C_, (13,), "params")
+    pol = np.asarray(policy_of_path)
+    if pol.shape != (M,) or not np.issubdtype(pol.dtype, np.integer):
+        raise ValueError(f"policy_of_path must hold {M} integers, one per path")
+    return ko, Kg, prm, np.ascontiguousarray(pol, np.int32), C_, nk, nK
+
+
+def ks_simulate_hist_multi(k_opt, k_grid, K_grid, x_grid, zi_paths, lam0, params,
+                           policy_of_path):
+    """ks_simulate_hist with one policy per path (host tier): k_opt (C, nk, nK, 4), K_grid
+    (C, nK), params (C, 13), policy_of_path (M,) integers in [0, C): path m runs candidate
+    policy_of_path[m].  Returns (K_ts (T, M), lam (M, 2, nx), slow_periods (M,))."""
+    kg = np.ascontiguousarray(k_grid, np.float64)
+    x = np.ascontiguousarray(x_grid, np.float64)
+    zi = np.asarray(zi_paths, np.float64)
+    zi = zi[:, None] if zi.ndim == 1 else zi
+    T, M = zi.shape
+    zi = np.asfortranarray(zi)
+    ko, Kg, prm, pol, C_, nk, nK = _multi_shapes(k_opt, kg, K_grid, params, policy_of_path, M)
+    kd = np.ascontiguousarray(ko.transpose(0, 3, 2, 1))    # each block k x K x 4 column-major
+    nx = x.size
+    lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (M, 2, nx)), order="C")
+    K_ts = np.empty((T, M), order="F")
+    slow = np.zeros(M, np.int64)
+    check(lib().ks_simulate_hist_multi(i64(C_), ptr(kd), ptr(kg), ptr(Kg), i64(nk), i64(nK),
+                                       ptr(x), i64(nx), ptr(prm), ptr(pol), ptr(zi), i64(T),
+                                       i64(M), ptr(lam), ptr(K_ts), ptr(slow)))
+    return K_ts, lam, slow
+
+
+class HistSimMulti:
+    """Device-resident histogram simulation with one policy per path: k_grid, x_grid, the M
+    shock paths and the distributions stay in HBM across calls; the candidates (policies, their
+    K_grid rows and params) and policy_of_path come with each call.  zi_paths (T, M) host array
+    in {0, 1}; lam0 (M, 2, nx) or (2, nx).  `lam` persists across calls; set_lam restarts it.  A
+    call with fewer than M entries in policy_of_path runs the first len(policy_of_path) paths."""
+
+    def __init__(self, k_grid, x_grid, zi_paths, lam0, device="cuda"):
+        import torch
+        dev = torch.device(device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.k_grid = torch.as_tensor(np.ascontiguousarray(k_grid, np.float64), **f64)
+        self.x_grid = torch.as_tensor(np.ascontiguousarray(x_grid, np.float64), **f64)
+        zi = np.asarray(zi_paths)
+        zi = zi[:, None] if zi.ndim == 1 else zi
+        if not np.all((zi == 0) | (zi == 1)):
+            raise ValueError("zi_paths must hold 0 (good) or 1 (bad)")
+        self.T, self.M = zi.shape
+        self.nx = self.x_grid.numel()
+        self.zi = torch.as_tensor(np.ascontiguousarray(zi.T.astype(np.int8)), device=dev)
+        self.lam = torch.empty((self.M, 2, self.nx), **f64)
+        self.set_lam(lam0)
+        self.K_ts = torch.empty((self.M, self.T), **f64)
+        self.slow = torch.zeros(self.M, dtype=torch.int64, device=dev)
+        self.scratch = None
+
+    def set_lam(self, lam0):
+        """lam0 (m, 2, nx), m <= M: the start of the first m paths; (2, nx): of every path."""
+        import torch
+        lam = np.asarray(lam0, np.float64)
+        if lam.ndim == 2:
+            lam = np.broadcast_to(lam, (self.M, 2, self.nx))
+        if lam.ndim != 3 or lam.shape[0] > self.M or lam.shape[1:] != (2, self.nx):
+            raise ValueError("lam0 must be (2, nx) or (m, 2, nx) with m <= M")
+        self.lam[:lam.shape[0]].copy_(torch.as_tensor(np.ascontiguousarray(lam)))
+
+    def __call__(self, k_opt, K_grid, params, policy_of_path, stream=None):
+        """One run.  k_opt: device [C][4][nK][nk]; K_grid: (C, nK) host array or device tensor;
+        params (C, 13) and policy_of_path (m,), m <= M, host.  Returns K_ts (device [m][T]);
+        self.lam[:m] holds the last period's distributions, self.slow[:m] the counts."""
+        import torch
+        C_, nS, nK, nk = k_opt.shape
+        if nS != 4 or nk != self.k_grid.numel():
+            raise ValueError("k_opt must be [C][4][K_size][numel(k_grid)]")
+        from .ks import _per_candidate
+        if not hasattr(K_grid, "data_ptr"):
+            K_grid = torch.as_tensor(np.array(_per_candidate(K_grid, C_, (nK,), "K_grid"),
+                                              order="C"), device=self.lam.device)
+        if tuple(K_grid.shape) != (C_, nK):
+            raise ValueError("K_grid must be (C, K_size)")
+        if not (k_opt.is_contiguous() and K_grid.is_contiguous()):
+            raise ValueError("k_opt and K_grid must be contiguous tensors")
+        prm = _per_candidate(params, C_, (13,), "params")
+        pol = np.asarray(policy_of_path)
+        m = pol.size
+        if pol.ndim != 1 or not 1 <= m <= self.M or not np.issubdtype(pol.dtype, np.integer):
+            raise ValueError(f"policy_of_path must hold 1..{self.M} integers, one per path")
+        pol = np.ascontiguousarray(pol, np.int32)
+        lib().ks_hist_multi_scratch_bytes.restype = C.c_int64
+        need = int(lib().ks_hist_multi_scratch_bytes(i64(C_), i64(m)))
+        if self.scratch is None or self.scratch.numel() < need:
+            self.scratch = torch.empty(need, dtype=torch.uint8, device=self.lam.device)
+        check(lib().ks_simulate_hist_multi_dev(i64(C_), i64(nk), i64(nK), ptr(self.k_grid),
+                                               ptr(K_grid), ptr(k_opt), ptr(self.x_grid),
+                                               i64(self.nx), ptr(prm), ptr(pol), ptr(self.zi),
+                                               i64(self.T), i64(m), ptr(self.lam),
+                                               ptr(self.K_ts), ptr(self.slow),
+                                               ptr(self.scratch), stream_handle(stream)))
+        return self.K_ts[:m]
+
+
 # ------------------------------------------------------------------ ALM loop (host)
 
 
@@ -364,6 +476,170 @@ def _krusell_smith_vfi_hist(prm, kg, Kg, P, V0, T, max_iter_B, tol_B, update_B, 
         B = update_B * B_new + (1 - update_B) * B                                # :295
     return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, value=value, k_opt=k_opt,
                 vfi_iters=vfi_iters, zi=zi, slow_periods=slow, x_grid=x)
+
+
+def _egm_economy(k_size, K_size, economy):
+    """(params, k_grid, K_grid, P) of one economy: ks_params keywords plus K_min and K_max."""
+    from . import calibration
+    from .ks import ks_params
+    eco = dict(economy)
+    K_min, K_max = eco.pop("K_min", 30.0), eco.pop("K_max", 50.0)
+    prm = ks_params(**eco)
+    kg, Kg, P, _ = calibration.krusell_smith(k_size=k_size, K_size=K_size, K_min=K_min,
+                                             K_max=K_max, beta=prm[0], k_min=prm[3],
+                                             k_max=prm[4], ug=prm[5], ub=prm[6])
+    return prm, kg, Kg, P
+
+
+def krusell_smith_egm(k_size=100, K_size=4, T=1100, population=10000, max_iter_B=100, tol_B=1e-6,
+                      update_B=0.3, tol_egm=1e-6, max_egm=10000, T_discard=100, uniforms=None,
+                      simulate="panel", n_paths=1, nx=1000, log=None, **economy):
+    """Krusell_Smith_EGM.m:95-301 end to end on the GPU kernels: shocks (F3), then per ALM
+    iteration the Gauss-Seidel EGM solve (A8, from the previous iteration's k_opt), the panel
+    simulation (F2, the population persisting, :99) and the host regression / damped update
+    (:255-300).  `economy`: ks_params keywords plus K_min and K_max (defaults: the script's).
+    Returns dict(B, B_history, R2, K_ts, k_opt, egm_iters, zi).
+    simulate="histogram": the histogram simulation on n_paths shock paths over an nx-point grid
+    in place of the panel, as krusell_smith_vfi's; K_ts and zi are then (T, n_paths) and
+    `uniforms` holds n_paths * (T - 1) aggregate draws."""
+    from .ks import ks_egm_solve
+    if simulate not in ("panel", "histogram"):
+        raise ValueError(f'simulate must be "panel" or "histogram", got {simulate!r}')
+    prm, kg, Kg, P = _egm_economy(k_size, K_size, economy)
+    hist_sim = simulate == "histogram"
+    if hist_sim:
+        import torch
+        ug = float(prm[5])
+        U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
+        zi = zi_paths(T, n_paths, U, prm)
+        x = hist_grid(nx, float(prm[3]), float(prm[4]))
+        sim = HistSim(kg, Kg, x, zi, hist_start(x, Kg[0], ug), prm)
+    else:
+        U = matlab_rand(shock_draws(T, population)) if uniforms is None else uniforms
+        zi, eps = ks_shocks(T, population, U, prm)
+        k_pop = np.full(population, Kg[0])                                      # :99
+    k_opt = 0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2)    # :96
+    B = np.array([0.0, 1.0, 0.0, 1.0])                                          # :97
+    hist, R2, K_ts, egm_iters, slow = [], (0.0, 0.0), None, [], None
+    for it in range(max_iter_B):
+        R = ks_egm_solve(k_opt, kg, Kg, B, P, prm, tol=tol_egm, max_iter=max_egm)
+        k_opt = R["k_opt"]
+        egm_iters.append(R["iters"])
+        if hist_sim:
+            ko_dev = torch.as_tensor(np.ascontiguousarray(k_opt.transpose(2, 1, 0)),
+                                     device=sim.lam.device)
+            K_ts = sim(ko_dev).cpu().numpy().T
+            slow = sim.slow.cpu().numpy()
+            sim.set_lam(hist_carry(sim.lam.cpu().numpy(), ug))
+            B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
+        else:
+            K_ts, k_pop = ks_simulate_capital(k_opt, kg, Kg, zi, eps, k_pop)
+            B_new, r2g, r2b = alm_regress(K_ts, zi, T_discard)
+        R2 = (r2g, r2b)
+        diff_B = float(np.max(np.abs(B_new - B)))                              # :291
+        hist.append(B_new.copy())
+        if log:
+            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
+        if diff_B < tol_B:
+            break
+        B = update_B * B_new + (1 - update_B) * B                                # :300
+    out = dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, k_opt=k_opt, egm_iters=egm_iters, zi=zi)
+    if hist_sim:
+        out.update(slow_periods=slow, x_grid=x)
+    return out
+
+
+def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=100, tol_B=1e-6,
+                            update_B=0.3, tol_egm=1e-6, max_egm=10000, T_discard=100,
+                            uniforms=None, n_paths=1, nx=1000, log=None):
+    """krusell_smith_egm(simulate="histogram") for several economies in lockstep.  `economies`:
+    a list of dicts of ks_params keywords plus K_min / K_max; all share k_min and k_max (hence
+    k_grid and x_grid), the sizes and the n_paths shock paths, each has its own params, P, K_grid
+    and B.  One ALM round is one ks_egm_solve_batch_dev over the economies still running (the
+    policies stay on the device), one histogram launch of (running economies) x n_paths
+    workgroups with one policy per path, K_ts back to the host and one pooled regression per
+    economy.  An economy leaves when its diff_B < tol_B, or when it fails: an EGM status != 0
+    (`failed` = "egm"; it is not simulated) or a non-positive or non-finite K_ts in the
+    regression window (`failed` = "K_ts").  Returns one dict per economy with
+    krusell_smith_egm's keys plus `failed` (None when it ran through); every economy that does
+    not fail equals its own krusell_smith_egm(simulate="histogram") run bit for bit."""
+    import torch
+    from .ks import ks_egm_solve_batch_dev
+    ecos = [_egm_economy(k_size, K_size, e) for e in economies]
+    E = len(ecos)
+    if E < 1:
+        raise ValueError("need at least one economy")
+    prm = np.stack([e[0] for e in ecos])
+    kg = ecos[0][1]
+    if np.any(prm[:, 3] != prm[0, 3]) or np.any(prm[:, 4] != prm[0, 4]):
+        raise ValueError("the economies of a batch share k_min and k_max (one k_grid and x_grid)")
+    Kg = np.stack([e[2] for e in ecos])
+    P = np.stack([e[3] for e in ecos])
+    ug = prm[:, 5]
+    U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
+    zi = zi_paths(T, n_paths, U, prm[0])
+    x = hist_grid(nx, float(prm[0, 3]), float(prm[0, 4]))
+    # path e * n_paths + p of the launch is shock path p: a prefix serves any number of economies
+    sim = HistSimMulti(kg, x, np.tile(zi, (1, E)), np.zeros((2, nx)))
+    dev = sim.lam.device
+    kg_dev = sim.k_grid
+    k0 = 0.9 * np.repeat(np.repeat(kg[None, None, :], K_size, 1), 4, 0)       # [4][nK][nk], :96
+    k_opt = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(k0, (E,) + k0.shape)),
+                            device=dev)
+    lam = np.stack([np.broadcast_to(hist_start(x, Kg[e, 0], ug[e]), (n_paths, 2, nx))
+                    for e in range(E)])
+    B = np.tile(np.array([0.0, 1.0, 0.0, 1.0]), (E, 1))                        # :97
+    res = [dict(B=B[e].copy(), B_history=[], R2=(0.0, 0.0), K_ts=None, k_opt=None, egm_iters=[],
+                zi=zi, slow_periods=None, x_grid=x, failed=None) for e in range(E)]
+    run = list(range(E))
+    for it in range(max_iter_B):
+        if not run:
+            break
+        idx = torch.as_tensor(run, device=dev)
+        ko = k_opt[idx]
+        iters, _, status, _ = ks_egm_solve_batch_dev(ko, kg_dev, Kg[run], B[run], P[run],
+                                                     prm[run], tol=tol_egm, max_iter=max_egm)
+        iters, status = iters.cpu().numpy(), status.cpu().numpy()
+        k_opt[idx] = ko
+        good = [r for r in range(len(run)) if status[r] == 0]
+        for r, e in enumerate(run):
+            res[e]["egm_iters"].append(int(iters[r]))
+            if status[r] != 0:
+                res[e]["failed"] = "egm"
+        K_all = slow = lam_new = None
+        if good:
+            sim.set_lam(np.concatenate([lam[run[r]] for r in good]))
+            pol = np.repeat(np.array(good, np.int32), n_paths)
+            K_all = sim(ko, Kg[run], prm[run], pol).cpu().numpy()
+            slow = sim.slow.cpu().numpy()
+            lam_new = sim.lam.cpu().numpy()
+        still = []
+        for g, r in enumerate(good):
+            e = run[r]
+            sl = slice(g * n_paths, (g + 1) * n_paths)
+            K_ts = K_all[sl].T
+            res[e].update(K_ts=K_ts, slow_periods=slow[sl].copy())
+            lam[e] = hist_carry(lam_new[sl], ug[e])
+            win = K_ts[T_discard - 1:]
+            if not (np.all(np.isfinite(win)) and np.all(win > 0)):
+                res[e]["failed"] = "K_ts"
+                continue
+            B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
+            res[e]["R2"] = (r2g, r2b)
+            diff_B = float(np.max(np.abs(B_new - B[e])))                       # :291
+            res[e]["B_history"].append(B_new.copy())
+            if log:
+                log(f"ALM {it + 1} economy {e}: B_new={B_new} diff={diff_B:.2e}")
+            if diff_B < tol_B:
+                continue
+            B[e] = update_B * B_new + (1 - update_B) * B[e]                      # :300
+            still.append(e)
+        run = still
+    ko_host = k_opt.cpu().numpy()
+    for e in range(E):
+        res[e]["B"] = B[e].copy()
+        res[e]["k_opt"] = np.asfortranarray(ko_host[e].transpose(2, 1, 0))
+    return res
 
 
 def hist_carry(lam, ug):

@@ -267,6 +267,22 @@ int ks_egm_solve_jacobi(double* k_opt, const double* k_grid, const double* K_gri
                         const double* B, const double* P, const double* params, int64_t nk,
                         int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff);
 
+/* A8 at C candidate economies in one launch: workgroup c runs ks_egm_solve's loop on candidate
+ * c's own k_opt with its own K_grid row, B, P and params; k_grid, the sizes, tol and max_iter are
+ * shared.  Layouts as ks_egm_solve, candidate-major: k_opt [C] of k x K x 4 column-major
+ * (in/out), K_grid [C][nK], B [C][4], P [C] of MATLAB 4 x 4, params [C][13]; iters, diff, status
+ * [C].  Every candidate's k_opt, iters and diff equal one ks_egm_solve call's bit for bit.
+ * The return code is about the call: status[c] = 1 marks a candidate that met fewer than 2 valid
+ * EGM points (ks_egm_solve's AIY_NON_FINITE; its k_opt slice is unspecified), the others are
+ * unaffected and the call returns AIY_OK.  Refused before any device work: NULL arguments, C
+ * outside [1, 65,535], k_size < 3, max_iter outside [1, 2^31), a size past the one-workgroup LDS
+ * rule of ks_egm_solve, a k_grid that is not strictly increasing, a K_grid row that is not
+ * positive and finite.  Scratch: the library's cached host-tier buffers. */
+int ks_egm_solve_batch(int64_t C, double* k_opt, const double* k_grid, const double* K_grid,
+                       const double* B, const double* P, const double* params, int64_t nk,
+                       int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
+                       int32_t* status);
+
 /* F3 — replaces the shock simulation Krusell_Smith_VFI.m:57-94 (also Krusell_Smith_EGM.m).
  * uniforms: the script's `rand` stream, ks_shock_draws(T, population) values in its draw order
  * (T-1 aggregate draws :63/:65, `population` draws :71, then (T-1)*population draws with t
@@ -304,6 +320,18 @@ int ks_simulate_hist(const double* k_opt, const double* k_grid, const double* K_
                      int64_t nK, const double* x_grid, int64_t nx, const double* params,
                      const double* zi_shock, int64_t T, int64_t M, double* lam, double* K_ts,
                      int64_t* slow_periods);
+/* The same with one policy per path: path m is simulated with candidate c = policy_of_path[m]
+ * (int32, 0-based, each in [0, C)): k_opt block c of [C] k x K x 4, row c of K_grid [C][K_size],
+ * and the employment transitions of params row c of [C][13].  k_grid, x_grid, T and the layouts
+ * of zi_shock, lam, K_ts and slow_periods are ks_simulate_hist's; path m's results equal one
+ * ks_simulate_hist call with candidate c alone bit for bit.  All of ks_simulate_hist's checks
+ * (per candidate where the input is), 1 <= C <= 65,535 and the range of policy_of_path are made
+ * before the device is touched. */
+int ks_simulate_hist_multi(int64_t C, const double* k_opt, const double* k_grid,
+                           const double* K_grid, int64_t nk, int64_t nK, const double* x_grid,
+                           int64_t nx, const double* params, const int32_t* policy_of_path,
+                           const double* zi_shock, int64_t T, int64_t M, double* lam,
+                           double* K_ts, int64_t* slow_periods);
 
 /* ======================================================================================
  * Device tier: [N][Na] (z-major) arrays in HBM, async on `stream` (hipStream_t).
@@ -692,6 +720,37 @@ int ks_simulate_hist_dev(int64_t nk, int64_t nK, const double* k_grid, const dou
                          const double* k_opt, const double* x_grid, int64_t nx,
                          const double* params, const int8_t* zi, int64_t T, int64_t M,
                          double* lam, double* K_ts, int64_t* slow_periods, void* stream);
+/* One policy per path on device (ks_simulate_hist_multi): k_opt [C][4][K_size][k_size] and
+ * K_grid [C][K_size] in HBM, the other device arrays as ks_simulate_hist_dev; params [C][13] and
+ * policy_of_path [M] are HOST arrays, validated (with the shapes) before the device is touched.
+ * scratch: ks_hist_multi_scratch_bytes(C, M) bytes of device memory owned by the caller, which
+ * receive the candidates' employment tables and policy_of_path; the call waits for that upload
+ * (one synchronisation of `stream`, so the host tables may die at return and a scratch still
+ * read by an earlier launch on the same stream is not overwritten early), then enqueues the one
+ * launch and returns. */
+int64_t ks_hist_multi_scratch_bytes(int64_t C, int64_t M);
+int ks_simulate_hist_multi_dev(int64_t C, int64_t nk, int64_t nK, const double* k_grid,
+                               const double* K_grid, const double* k_opt, const double* x_grid,
+                               int64_t nx, const double* params, const int32_t* policy_of_path,
+                               const int8_t* zi, int64_t T, int64_t M, double* lam, double* K_ts,
+                               int64_t* slow_periods, void* scratch, void* stream);
+
+/* ---- A8 batch device tier (ks_egm_solve_batch): k_opt [C][4][K_size][k_size] (in/out), k_grid,
+ * iters (int64), diff and status (int32) [C] in HBM; K_grid [C][K_size], B [C][4], P [C] of
+ * MATLAB 4 x 4 and params [C][13] are HOST arrays (the per-pair scalars are libm on the host, as
+ * in ks_egm_solve).  Host arguments and shapes are validated before any device work; the
+ * contents of k_grid (strictly increasing) are the caller's.
+ * Scratch ownership: the host tier stages everything in the library's cached buffers; this tier
+ * owns none — scratch is ks_egm_batch_scratch_bytes(C, K_size) bytes of device memory owned by
+ * the caller and receives the host-built candidate tables.  The call waits for that upload (one
+ * synchronisation of `stream`: the host tables die at return, and a scratch still read by an
+ * earlier solve on the same stream is not overwritten early), then enqueues the one launch and
+ * returns; the outputs are valid once `stream` has run it. */
+int64_t ks_egm_batch_scratch_bytes(int64_t C, int64_t nK);
+int ks_egm_solve_batch_dev(int64_t C, double* k_opt, const double* k_grid, const double* K_grid,
+                           const double* B, const double* P, const double* params, int64_t nk,
+                           int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
+                           int32_t* status, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }
