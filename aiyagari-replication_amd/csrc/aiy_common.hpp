@@ -108,6 +108,11 @@ __device__ __forceinline__ int wave_max_i32_lane63(int k) {
     k = max(k, (int)dpp_u32<0x143, 0xc>((unsigned)k));
     return k;
 }
+// min over the wave of a 32-bit signed key (> INT_MIN) as a wave-uniform value: the ladder
+// above on the negated key
+__device__ __forceinline__ int wave_min_i32(int k) {
+    return -readlane_i(wave_max_i32_lane63(-k), 63);
+}
 
 // first k in [0, n) with a[k] >= x  (== count of a[k] < x), a non-decreasing.
 __device__ __forceinline__ int lower_bound_dev(const double* __restrict__ a, int n, double x) {
@@ -161,6 +166,10 @@ __device__ __forceinline__ unsigned long long nonneg_key(double x) {
 // the block's waves, then ONE atomicMax per block on IEEE bits (order-independent, hence
 // deterministic) into slot blockIdx % kDiffSlots, so no single address is contended.
 constexpr int kDiffSlots = 64;
+// the work counters (BellArgs::hitcount): four per slot, then from kPathBase on the tree
+// kernel's fine-screen blocks per body, four per slot again
+constexpr int kPathBase = 4 * kDiffSlots;
+constexpr int kHitcountLen = 8 * kDiffSlots;
 __device__ __forceinline__ void block_max_to_slots(bool ok, double d,
                                                    unsigned long long* __restrict__ slots) {
     __shared__ unsigned long long s_key[16];

@@ -61,14 +61,18 @@ __device__ __forceinline__ double bell_val(double c, double ev, double sigma, do
 // compiler emits each pair's 5-deep chain back to back and the wave stalls on every op.  The
 // operation sequence per pair is aiy_ipow's, so every t is the unstaged expression's bit for
 // bit and the screen's rounding analysis is unchanged.
+// CLAMP = false drops the max stage (c = cx): for callers that know cx > 0 in every lane whose
+// result counts, where fmax(cx, 0) == cx bit for bit.  With cx = coh − a_k that is every
+// candidate below the lane's feasible prefix kf = #{k : a_k < coh}: in IEEE fp64 the difference
+// of two distinct doubles is never zero (subnormals included), so coh − a_k > 0 ⟺ a_k < coh.
 #define AIY_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-template <int NP, int M>
+template <int NP, int M, bool CLAMP = true>
 __device__ __forceinline__ void screen_t(double (&t)[M], const double (&cx)[M],
                                          const double (&dd)[M]) {
     double c[M], p[M];
 #pragma unroll
-    for (int m = 0; m < M; ++m) c[m] = fmax(cx[m], 0.0);
-    AIY_SCHED_BARRIER();
+    for (int m = 0; m < M; ++m) c[m] = CLAMP ? fmax(cx[m], 0.0) : cx[m];
+    if constexpr (CLAMP) AIY_SCHED_BARRIER();
 #pragma unroll
     for (int m = 0; m < M; ++m) p[m] = c[m];
     constexpr int top = 31 - __builtin_clz((unsigned)NP);
@@ -85,6 +89,20 @@ __device__ __forceinline__ void screen_t(double (&t)[M], const double (&cx)[M],
     }
 #pragma unroll
     for (int m = 0; m < M; ++m) t[m] = dd[m] * p[m];
+}
+// screen_t's clamp stage on its own, for callers that branch around it (wave-uniformly) and
+// then run screen_t<NP, M, false>: max(x, 0) of an x that is the result of an fp64 subtraction
+// — canonical already — as the one v_max_f64 the compiler emits for fmax(x, 0.0) inside
+// screen_t.  Across a branch it no longer sees where x came from and would add a second,
+// canonicalising v_max_f64 x, x in front; the result is the same either way.
+__device__ __forceinline__ double clamp0_d(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    double r;
+    asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return fmax(x, 0.0);
+#endif
 }
 // pairs per stage group: 8 candidates × the sub-states of a lane, at most ~16 chains
 template <int RL>

@@ -48,7 +48,9 @@ struct BellArgs {
     int* touched;   // [N][Na] 1 when some chunk wrote `partial` for the state this sweep
     unsigned long long* hitcount;  // nullable, [4]: exact evals, superblock, block, fine tests
                                    // (lane-level evaluations executed; the tree's wave-level
-                                   // superblock test counts its 64 lanes once)
+                                   // superblock test counts its 64 lanes once); the tree kernel
+                                   // also counts its fine-screen blocks per body in a second
+                                   // set of slots, kPathBase on (aiy_ws_screen_paths)
     long long* trace;  // nullable: per tree work item {t0, t1, xcc, nsup, nblk, nfine, nhits, item}
                        // (nsup: superblocks entered)
     // outputs
@@ -105,6 +107,8 @@ constexpr int kEgmTwoLaunch = 1 << 18;   // the two-launch step even for Na <= 1
 constexpr int kEgmNoChain = 1 << 19;     // solve loop: two launches per step, no chaining
 constexpr int kEgmNoHints = 1 << 20;     // interp1 without the previous step's segment windows
 constexpr int kVarDriftExtrap = 1 << 21; // start-up extrapolates the drift from the last two shifts
+constexpr int kVarPlainScreens = 1 << 22;  // tree: every screen keeps the clamp (no identity
+                                           // fast path; equality tests and one-build A/B)
 constexpr int kVarHintAlone = 1 << 23;   // the hint's window is the hint alone when the
                                          // extrapolated window is evaluated
 constexpr int kVarNoHintEval = 1 << 24;  // (with kVarHintAlone) not even the hint then
@@ -126,7 +130,7 @@ constexpr int kVarFields[] = {
     kVarR2, kVarWavesMask, kVarChunked, kVarXcdOrder, kVarNoClimb, kVarPermHeavy, kVarHintWinMask,
     kVarNoMomentum, kVarExhaustive, kVarPermCheapLast, kVarDealBlocks, kVarNarrowTiles, kVarEvValu,
     kVarEvMfma, kVarPackMask, kEgmTwoLaunch, kEgmNoChain, kEgmNoHints, kVarDriftExtrap,
-    kVarHintAlone, kVarNoHintEval, kVarWide, kVarHybrid, kVarCoopMask};
+    kVarPlainScreens, kVarHintAlone, kVarNoHintEval, kVarWide, kVarHybrid, kVarCoopMask};
 constexpr bool var_fields_disjoint() {
     long long sum = 0, all = 0;
     for (int f : kVarFields) sum += f, all |= f;

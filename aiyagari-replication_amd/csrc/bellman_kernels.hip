@@ -967,6 +967,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     // evaluations each, whatever the number of sub-states)
     // ngt: group-level tests of the 8-block bounds (64 lane evaluations each, like nwv)
     unsigned nhits = nsu, nsup = 0, nwv = 0, nblk = 0, ngt = 0, nfine = 0, lane_pairs = 0;
+    unsigned npath[2] = {0, 0};  // fine-screen blocks with the clamp, without it
     const long long t_start = (INS && A.trace) ? (long long)wall_clock64() : 0;
     // phase cycle counters (trace mode): startup, superblock() calls, fine screens, exact paths
     long long cyc[4] = {0, 0, 0, 0}, c_mark = (INS && A.trace) ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -1000,6 +1001,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
     for (int l0 = 0; l0 < Nl; l0 += LB) {  // labour levels in groups of LB sub-states per lane
         double coh[R][LB], B[R][LB], dis[LB];
         int kg = 0;  // the group's feasible range over the tile (identical in every wave)
+        int kfl = 0x7fffffff;  // the smallest feasible prefix of this lane's valid sub-states
 #pragma unroll
         for (int q = 0; q < LB; ++q) dis[q] = (LAB && l0 + q < Nl) ? A.dis[l0 + q] : 0.0;
 #pragma unroll
@@ -1009,9 +1011,28 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             for (int q = 0; q < LB; ++q) {
                 const bool okq = okr[r] && l0 + q < Nl;
                 coh[r][q] = okq ? cash<LAB>(x[r], y, LAB ? A.L[l0 + q] : 1.0) : 0.0;
-                if (okq) kg = max(kg, A.kf[(l0 + q) * nall + t]);
+                if (okq) {
+                    const int kfv = A.kf[(l0 + q) * nall + t];
+                    kg = max(kg, kfv);
+                    kfl = min(kfl, kfv);
+                }
             }
         }
+        // The clamp's fast path (FAST).  kfmin: the smallest feasible
+        // prefix kf = #{k : a_k < coh} over the wave's valid sub-states, wave-uniform (invalid
+        // ones count as +inf; a ladder over all lanes: the minimum sits in the first valid lane
+        // only while 1 + r > 0).  For a candidate k < kfmin every valid sub-state has
+        // a_k < coh, hence cx = coh − a_k > 0 and fmax(cx, 0) == cx bit for bit: the fine
+        // screen of a block below kfmin runs without the clamp.  An invalid sub-state has cash
+        // 0 and a NaN bar: dd = D − NaN is NaN and t = dd·p is NaN for every p, clamped or not,
+        // so its test is false in both bodies; a valid one with idx < 0 has B = −inf,
+        // dd = +inf and p > 0 below kfmin, so it passes in both.  Variant bit 22 sets
+        // kfmin = 0: every block keeps the clamp.  Labour keeps its body unchanged, and so
+        // do the two-states-per-lane tiles (R = 2: the branch cost those builds scratch).
+        constexpr bool FAST = !LAB && R == 1;
+        int kfmin = 0;
+        if constexpr (FAST)
+            if (!(A.variant & kVarPlainScreens)) kfmin = min(wave_min_i32(kfl), Na);
         if (A.r > -1.0) {
             // coh is increasing in j when 1 + r > 0, so every feasible prefix kf is
             // non-decreasing along the tile: the maximum sits in the last valid lane
@@ -1113,9 +1134,15 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk) tk[kk] = s_cand[lw][(bit << 3) + kk];
         };
+        // The clamp's fast path (FAST; same t, pass bits and votes from eight fewer VALU
+        // instructions): the clamp stage is skipped, by a wave-uniform branch around it, when
+        // all eight staged candidates lie below kfmin — all eight, not only those below k1:
+        // the first wave vote looks at the unmasked eight.
         auto fine = [&](int sbase, int k0, int k1, const double2 (&tk)[8])
                         __attribute__((always_inline)) {
             if (INS && (A.hitcount || A.trace)) nfine += k1 - k0;
+            const bool ncl = FAST && k0 + 8 <= kfmin;
+            if (INS && A.hitcount) npath[0] += ncl ? 0u : 1u, npath[1] += ncl ? 1u : 0u;
             bool pk[8];
 #pragma unroll
             for (int g0 = 0; g0 < 8; g0 += G) {
@@ -1131,7 +1158,16 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                             dd[m] = tk[g0 + gk].y - B[r][q];
                         }
                 AIY_SCHED_BARRIER();
-                screen_t<NP, G * RL>(t, cx, dd);
+                if constexpr (FAST) {
+                    if (!ncl) {  // screen_t's clamp stage, then the rest of it
+#pragma unroll
+                        for (int m = 0; m < G * RL; ++m) cx[m] = clamp0_d(cx[m]);
+                        AIY_SCHED_BARRIER();
+                    }
+                    screen_t<NP, G * RL, false>(t, cx, dd);
+                } else {
+                    screen_t<NP, G * RL>(t, cx, dd);
+                }
 #pragma unroll
                 for (int gk = 0; gk < G; ++gk) {
                     bool pass = false;
@@ -1598,6 +1634,9 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             atomicAdd(hc + 1, nwv * 64ull);
             atomicAdd(hc + 2, nblk * ns + ngt * 64ull);
             if (nfine) atomicAdd(hc + 3, nfine * ns);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                if (npath[q]) atomicAdd(hc + kPathBase + q, (unsigned long long)npath[q]);
         }
     }
 }

@@ -81,9 +81,9 @@ int ws_ensure_bell(aiy_ws* ws, size_t partial_slots) {
     AIY_TRY(ws->partial.ensure(partial_slots, &fresh));
     if (fresh) AIY_HIP(hipMemset(ws->partial, 0xff, partial_slots * sizeof(int)));
     AIY_TRY(ws_ensure_diff(ws));  // (here: the device allocations keep the order they always had)
-    AIY_TRY(ws->hitcount.ensure(4 * kDiffSlots, &fresh));
+    AIY_TRY(ws->hitcount.ensure(kHitcountLen, &fresh));
     if (fresh)  // zero from the start: counting may be switched on before a sweep
-        AIY_HIP(hipMemset(ws->hitcount, 0, 4 * kDiffSlots * sizeof(unsigned long long)));
+        AIY_HIP(hipMemset(ws->hitcount, 0, kHitcountLen * sizeof(unsigned long long)));
     return ws->dis.ensure((size_t)std::max<int64_t>(ws->Nl, 1));
 }
 
@@ -907,7 +907,7 @@ int aiy_ws_set_timing(aiy_ws* ws, int enable) {
     ws->tracing = (enable & 4) != 0;
     ws->tot_ms = 0;
     ws->launches = 0;
-    if (ws->hitcount) AIY_HIP(hipMemset(ws->hitcount, 0, 4 * kDiffSlots * sizeof(unsigned long long)));
+    if (ws->hitcount) AIY_HIP(hipMemset(ws->hitcount, 0, kHitcountLen * sizeof(unsigned long long)));
     if (ws->tracing && ws->trace)  // records of an earlier geometry must not linger
         AIY_HIP(hipMemset(ws->trace, 0, ws->trace.cap() * sizeof(long long)));
     return AIY_OK;
@@ -935,6 +935,20 @@ int aiy_ws_counters(aiy_ws* ws, int64_t out[4]) {
     for (int q = 0; q < 4; ++q) {
         unsigned long long t = 0;
         for (int sl = 0; sl < kDiffSlots; ++sl) t += h[4 * sl + q];
+        out[q] = (int64_t)t;
+    }
+    return AIY_OK;
+}
+
+int aiy_ws_screen_paths(aiy_ws* ws, int64_t out[2]) {
+    if (!ws || !out) return fail(AIY_BAD_ARG, "NULL workspace/out");
+    std::vector<unsigned long long> h(kHitcountLen, 0ull);
+    if (ws->hitcount)
+        AIY_HIP(hipMemcpy(h.data(), ws->hitcount, h.size() * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost));
+    for (int q = 0; q < 2; ++q) {
+        unsigned long long t = 0;
+        for (int sl = 0; sl < kDiffSlots; ++sl) t += h[kPathBase + 4 * sl + q];
         out[q] = (int64_t)t;
     }
     return AIY_OK;

@@ -124,7 +124,7 @@ struct aiy_ws {
     bool perm_ok = false;
     Dev<int> partial;
     Dev<u64> diff;           // device [2*kDiffSlots] {max bits, any}   (ws_ensure_diff)
-    Dev<u64> hitcount;       // device [4 * kDiffSlots]
+    Dev<u64> hitcount;       // device [kHitcountLen]
     Dev<long long> trace;    // device [16 * units] (instrumentation; ws_ensure_trace)
     bool tracing = false;
     aiy::PinnedBuf<u64> hdiff;  // pinned host [2*kDiffSlots + 4]

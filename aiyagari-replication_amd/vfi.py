@@ -116,6 +116,13 @@ class Workspace:
         check(lib().aiy_ws_counters(self._h, out))
         return tuple(int(x) for x in out)
 
+    def screen_paths(self):
+        """8-candidate blocks of the tree sweep's candidate screen since set_timing(count=True),
+        by body: (with the clamp, without it)."""
+        out = (C.c_int64 * 2)()
+        check(lib().aiy_ws_screen_paths(self._h, out))
+        return tuple(int(x) for x in out)
+
     def invalidate(self):
         """Drop the cached feasibility table (after overwriting a_grid/s/L in place)."""
         check(lib().aiy_ws_invalidate(self._h))

@@ -350,6 +350,10 @@ int aiy_ws_timing(aiy_ws* ws, double* total_ms, int64_t* launches, int64_t* hits
  * candidate evaluations, out[1] superblock (512-candidate) tests, out[2] block (64) tests,
  * out[3] candidates screened individually — each counted per state.  Instrumentation only. */
 int aiy_ws_counters(aiy_ws* ws, int64_t out[4]);
+/* 8-candidate blocks the tree sweep's candidate screen ran since aiy_ws_set_timing(ws, 2), by
+ * body: out[0] with the clamp max(c, 0), out[1] without it (the block lies below every feasible
+ * prefix of its wave, where the clamp is the identity).  Instrumentation only. */
+int aiy_ws_screen_paths(aiy_ws* ws, int64_t out[2]);
 /* per-work-item trace of the last tree sweep (aiy_ws_set_timing bit 2): 16 int64 per item
  * {start clock, end clock (100 MHz wall clock), XCD id, superblock tests, block tests,
  * candidates, exact evaluations, hardware block id, wave-0 shader cycles in: startup and
@@ -399,7 +403,8 @@ int aiy_ws_set_sim(aiy_ws* ws, int mode);
  * XCD's tile range and deals it heaviest first / row-major with its cheapest tiles last, bit 13 =
  * one-wave tiles narrowed to ceil(N·Na / 3072) states (>= 16), bits 16-17 = (with bit 6 or
  * 11, A1 at sigma = 5) 1, 2, 4 or 8 one-wave tiles per workgroup, bit 21 = the start-up
- * extrapolates the argmax drift from the last two sweeps' shifts (else the last shift), bit 23 =
+ * extrapolates the argmax drift from the last two sweeps' shifts (else the last shift), bit 22 =
+ * every screen keeps its clamp (no identity fast path: A/B and tests), bit 23 =
  * the hint's own window is the hint alone when the extrapolated window is evaluated, bit 24
  * (with 23) = not even the hint then;
  * bit 3 set: the chunked screen + merge, with bit 0 = 4 states per lane (else 2), bit 1 =
