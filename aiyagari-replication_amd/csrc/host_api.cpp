@@ -21,27 +21,14 @@ static std::mutex g_mu;
 static std::map<std::tuple<int, int64_t, int64_t, int64_t>, std::unique_ptr<HostCtx>> g_ctx;
 
 HostCtx::~HostCtx() {
-    for (auto& kv : bufs) (void)hipFree(kv.second.first);
+    bufs.m.clear();  // the buffers first, then the workspace and the stream they were used on
     if (ws) aiy_ws_destroy(ws);
     if (st) (void)hipStreamDestroy(st);
 }
 
-int HostCtx::buf(const char* name, size_t bytes, void** out) {
-    auto it = bufs.find(name);
-    if (it != bufs.end() && it->second.second >= bytes) {
-        *out = it->second.first;
-        return AIY_OK;
-    }
-    if (it != bufs.end()) {
-        (void)hipFree(it->second.first);
-        bufs.erase(it);
-    }
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-    if (e != hipSuccess) return fail(AIY_NO_MEMORY, "hipMalloc(%zu) failed", bytes);
-    bufs[name] = {p, bytes};
-    *out = p;
-    return AIY_OK;
+int copy_status(hipError_t e, const char* what) {
+    if (e == hipSuccess) return AIY_OK;
+    return fail(AIY_HIP_ERROR, "hipMemcpyAsync (%s) failed: %s", what, hipGetErrorString(e));
 }
 
 int get_ctx(int64_t N, int64_t Na, int64_t Nl, HostCtx** out) {
@@ -272,8 +259,7 @@ int aiy_release_all(void) {
 int64_t aiy_host_cache_bytes(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     int64_t b = 0;
-    for (auto& kv : g_ctx)
-        for (auto& q : kv.second->bufs) b += (int64_t)q.second.second;
+    for (auto& kv : g_ctx) b += (int64_t)kv.second->bufs.bytes();
     return b;
 }
 

@@ -64,6 +64,63 @@ static void ks_egm_pairs(const double* prm, const double* K_grid, const double* 
     }
 }
 
+void p_rows(const double* P, double out[16]) {
+    for (int i = 0; i < 4; ++i)
+        for (int m = 0; m < 4; ++m) out[i * 4 + m] = P[i + m * 4];
+}
+
+// the pair tables take log(K) and K^(alpha - 1); cand > 0 (the batch tiers) names the candidate
+static int check_K_grid_positive(const double* K_grid, int64_t nK, int64_t cand = 0) {
+    for (int64_t q = 0; q < nK; ++q)
+        if (!(K_grid[q] > 0) || !std::isfinite(K_grid[q]))
+            return cand ? fail(AIY_NON_FINITE, "K_grid must be positive and finite (candidate %lld)",
+                               (long long)cand)
+                        : fail(AIY_NON_FINITE, "K_grid must be positive and finite");
+    return AIY_OK;
+}
+
+static int no_egm_points() {
+    return fail(AIY_NON_FINITE, "an (s, K) pair had fewer than 2 valid EGM points "
+                                "(griddedInterpolant needs two; Krusell_Smith_EGM.m:196)");
+}
+
+// What ks_egm_solve and ks_egm_solve_jacobi stage alike, behind their own checks.  The host
+// copies live here until the caller's next wait on the stream.
+struct EgmStage {
+    std::vector<KsEgmPair> pairs;
+    double Pr[16];
+    KsEgmArgs A{};
+    double* dk = nullptr;  // the policy buffer, holding k_opt in its first k x K x S block
+};
+// k_grid, P as rows, k_opt and the pair table up, into the buffers <pre>kg, <pre>P, `pol_name`
+// (room for `slots` policies: the Jacobi ring, whose slot 0 is the start) and <pre>pairs.
+static int egm_stage(HostCtx* c, const std::string& pre, const char* pol_name, size_t slots,
+                     const double* k_opt, const double* k_grid, const double* K_grid,
+                     const double* B, const double* P, const double* params, int64_t nk,
+                     int64_t nK, double tol, int64_t max_iter, EgmStage& S) {
+    ks_egm_pairs(params, K_grid, B, (int)nK, S.pairs);
+    p_rows(P, S.Pr);
+    const size_t n = (size_t)nk * nK * 4;
+    double *dkg, *dP;
+    KsEgmPair* dpairs;
+    AIY_TRY(c->up((pre + "kg").c_str(), k_grid, nk, &dkg));
+    AIY_TRY(c->up((pre + "P").c_str(), S.Pr, 16, &dP));
+    AIY_TRY(c->room(pol_name, slots * n, &S.dk));
+    AIY_TRY(c->up(pol_name, k_opt, n, &S.dk));  // (fits: the same memory)
+    AIY_TRY(c->up((pre + "pairs").c_str(), S.pairs.data(), S.pairs.size(), &dpairs));
+    S.A.nk = (int)nk;
+    S.A.nK = (int)nK;
+    S.A.max_iter = (int)max_iter;
+    S.A.k_grid = dkg;
+    S.A.P = dP;
+    S.A.pairs = dpairs;
+    S.A.beta = params[0];
+    S.A.k_min = params[3];
+    S.A.k_max = params[4];
+    S.A.tol = tol;
+    return AIY_OK;
+}
+
 // ---- the batched solve: C economies, one workgroup each (ks_egm_solve_batch_kernel)
 
 // what both tiers check on their host arguments, before any device work
@@ -75,11 +132,7 @@ static int check_egm_batch(int64_t C, const double* K_grid, int64_t nk, int64_t 
     if (max_iter < 1 || max_iter > 2147483647) return fail(AIY_BAD_ARG, "max_iter in [1, 2^31)");
     if (!ks_egm_fits((int)nk, (int)nK))
         return fail(AIY_BAD_SHAPE, "k_size x K_size too large for the one-workgroup EGM solve");
-    for (int64_t c = 0; c < C; ++c)
-        for (int64_t q = 0; q < nK; ++q)
-            if (!(K_grid[c * nK + q] > 0) || !std::isfinite(K_grid[c * nK + q]))
-                return fail(AIY_NON_FINITE, "K_grid must be positive and finite (candidate %lld)",
-                            (long long)(c + 1));
+    for (int64_t c = 0; c < C; ++c) AIY_TRY(check_K_grid_positive(K_grid + c * nK, nK, c + 1));
     return AIY_OK;
 }
 
@@ -102,8 +155,7 @@ static int egm_batch_dev(int64_t C, double* k_opt, const double* k_grid, const d
         const double* prm = params + 13 * c;
         ks_egm_pairs(prm, K_grid + c * nK, B + 4 * c, (int)nK, one);
         std::copy(one.begin(), one.end(), pairs.begin() + (size_t)c * 4 * nK);
-        for (int i = 0; i < 4; ++i)
-            for (int m = 0; m < 4; ++m) cand[c].P[i * 4 + m] = P[16 * c + i + m * 4];
+        p_rows(P + 16 * c, cand[c].P);
         cand[c].beta = prm[0];
         cand[c].k_min = prm[3];
         cand[c].k_max = prm[4];
@@ -168,21 +220,19 @@ int ks_egm_solve_batch(int64_t C, double* k_opt, const double* k_grid, const dou
     double *dkg, *dk, *ddiff;
     int64_t* dit;
     int32_t* dst;
-    void* dscr;
-    AIY_TRY(c->buf("egmb_kg", nk * sizeof(double), (void**)&dkg));
-    AIY_TRY(c->buf("egmb_k", n * sizeof(double), (void**)&dk));
-    AIY_TRY(c->buf("egmb_iters", C * sizeof(int64_t), (void**)&dit));
-    AIY_TRY(c->buf("egmb_diff", C * sizeof(double), (void**)&ddiff));
-    AIY_TRY(c->buf("egmb_status", C * sizeof(int32_t), (void**)&dst));
-    AIY_TRY(c->buf("egmb_scratch", egm_batch_scratch(C, nK), &dscr));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dk, k_opt, n * sizeof(double), hipMemcpyHostToDevice, c->st));
+    unsigned char* dscr;
+    AIY_TRY(c->up("egmb_kg", k_grid, nk, &dkg));
+    AIY_TRY(c->up("egmb_k", k_opt, n, &dk));
+    AIY_TRY(c->room("egmb_iters", C, &dit));
+    AIY_TRY(c->room("egmb_diff", C, &ddiff));
+    AIY_TRY(c->room("egmb_status", C, &dst));
+    AIY_TRY(c->room("egmb_scratch", egm_batch_scratch(C, nK), &dscr));
     AIY_TRY(egm_batch_dev(C, dk, dkg, K_grid, B, P, params, nk, nK, tol, max_iter, dit, ddiff, dst,
                           dscr, c->st));
-    AIY_HIP(hipMemcpyAsync(iters, dit, C * sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(diff, ddiff, C * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(status, dst, C * sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(k_opt, dk, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(iters, dit, C));
+    AIY_TRY(c->down(diff, ddiff, C));
+    AIY_TRY(c->down(status, dst, C));
+    AIY_TRY(c->down(k_opt, dk, n));
     AIY_HIP(hipStreamSynchronize(c->st));
     return AIY_OK;
 }
@@ -198,53 +248,23 @@ int ks_egm_solve(double* k_opt, const double* k_grid, const double* K_grid, cons
     if (!ks_egm_fits((int)nk, (int)nK))
         return fail(AIY_BAD_SHAPE, "k_size x K_size too large for the one-workgroup EGM solve");
     AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
-    for (int64_t q = 0; q < nK; ++q)
-        if (!(K_grid[q] > 0) || !std::isfinite(K_grid[q]))
-            return fail(AIY_NON_FINITE, "K_grid must be positive and finite");
+    AIY_TRY(check_K_grid_positive(K_grid, nK));
     std::lock_guard<std::mutex> lk(host_mutex());
     HostCtx* c;
     AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
-    std::vector<KsEgmPair> pairs;
-    ks_egm_pairs(params, K_grid, B, (int)nK, pairs);
-    double Pr[16];
-    for (int i = 0; i < 4; ++i)
-        for (int m = 0; m < 4; ++m) Pr[i * 4 + m] = P[i + m * 4];
-    const size_t n = (size_t)nk * nK * 4;
-    double *dkg, *dP, *dk;
-    KsEgmPair* dpairs;
+    EgmStage S;
+    AIY_TRY(egm_stage(c, "egm_", "egm_k", 1, k_opt, k_grid, K_grid, B, P, params, nk, nK, tol,
+                      max_iter, S));
     KsEgmOut* dout;
-    AIY_TRY(c->buf("egm_kg", nk * sizeof(double), (void**)&dkg));
-    AIY_TRY(c->buf("egm_P", sizeof Pr, (void**)&dP));
-    AIY_TRY(c->buf("egm_k", n * sizeof(double), (void**)&dk));
-    AIY_TRY(c->buf("egm_pairs", pairs.size() * sizeof(KsEgmPair), (void**)&dpairs));
-    AIY_TRY(c->buf("egm_out", sizeof(KsEgmOut), (void**)&dout));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dP, Pr, sizeof Pr, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dk, k_opt, n * sizeof(double), hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dpairs, pairs.data(), pairs.size() * sizeof(KsEgmPair),
-                           hipMemcpyHostToDevice, c->st));
-    KsEgmArgs A{};
-    A.nk = (int)nk;
-    A.nK = (int)nK;
-    A.max_iter = (int)max_iter;
-    A.k_grid = dkg;
-    A.P = dP;
-    A.pairs = dpairs;
-    A.beta = params[0];
-    A.k_min = params[3];
-    A.k_max = params[4];
-    A.tol = tol;
-    AIY_TRY(launch_ks_egm_solve(A, dk, dout, c->st));
+    AIY_TRY(c->room("egm_out", 1, &dout));
+    AIY_TRY(launch_ks_egm_solve(S.A, S.dk, dout, c->st));
     KsEgmOut o;
-    AIY_HIP(hipMemcpyAsync(&o, dout, sizeof o, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(k_opt, dk, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(&o, dout, 1));
+    AIY_TRY(c->down(k_opt, S.dk, (size_t)nk * nK * 4));
     AIY_HIP(hipStreamSynchronize(c->st));
     *iters = o.iters;
     *diff = o.diff;
-    if (o.status)
-        return fail(AIY_NON_FINITE, "an (s, K) pair had fewer than 2 valid EGM points "
-                                    "(griddedInterpolant needs two; Krusell_Smith_EGM.m:196)");
-    return AIY_OK;
+    return o.status ? no_egm_points() : AIY_OK;
 }
 
 // F1 — the Jacobi variant of the KS EGM iteration: every (s, K) pair of a sweep reads the
@@ -261,41 +281,25 @@ int ks_egm_solve_jacobi(double* k_opt, const double* k_grid, const double* K_gri
         return fail(AIY_BAD_SHAPE, "k_size too large for one workgroup per (s, K) pair");
     if (max_iter < 1 || max_iter > 2147483647) return fail(AIY_BAD_ARG, "max_iter in [1, 2^31)");
     AIY_TRY(check_grid_strict(k_grid, nk));  // pchip divides by k(i+1) - k(i)
-    for (int64_t q = 0; q < nK; ++q)
-        if (!(K_grid[q] > 0) || !std::isfinite(K_grid[q]))
-            return fail(AIY_NON_FINITE, "K_grid must be positive and finite");
+    AIY_TRY(check_K_grid_positive(K_grid, nK));
     std::lock_guard<std::mutex> lk(host_mutex());
     HostCtx* c;
     AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
-    std::vector<KsEgmPair> pairs;
-    ks_egm_pairs(params, K_grid, B, (int)nK, pairs);
-    double Pr[16];
-    for (int i = 0; i < 4; ++i)
-        for (int m = 0; m < 4; ++m) Pr[i * 4 + m] = P[i + m * 4];
     const size_t n = (size_t)nk * nK * 4;
     constexpr int kBatch = 16;
     // ring of kBatch + 1 policy buffers: sweep g reads slot (g-1) % R and writes slot g % R, so
     // the sweeps a batch runs past the stopping sweep never overwrite its output
     constexpr int R = kBatch + 1;
-    double *dkg, *dP, *ring;
-    KsEgmPair* dpairs;
+    EgmStage S;
+    AIY_TRY(egm_stage(c, "egmj_", "egmj_ring", R, k_opt, k_grid, K_grid, B, P, params, nk, nK,
+                      tol, max_iter, S));
+    const KsEgmArgs& A = S.A;
+    double* const ring = S.dk;
     unsigned long long* dslots;
     int* dstatus;
-    AIY_TRY(c->buf("egmj_kg", nk * sizeof(double), (void**)&dkg));
-    AIY_TRY(c->buf("egmj_P", sizeof Pr, (void**)&dP));
-    AIY_TRY(c->buf("egmj_ring", (size_t)R * n * sizeof(double), (void**)&ring));
-    AIY_TRY(c->buf("egmj_pairs", pairs.size() * sizeof(KsEgmPair), (void**)&dpairs));
-    AIY_TRY(c->buf("egmj_slots", kBatch * 2 * kDiffSlots * sizeof(unsigned long long), (void**)&dslots));
-    AIY_TRY(c->buf("egmj_status", sizeof(int), (void**)&dstatus));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dP, Pr, sizeof Pr, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(ring, k_opt, n * sizeof(double), hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dpairs, pairs.data(), pairs.size() * sizeof(KsEgmPair),
-                           hipMemcpyHostToDevice, c->st));
+    AIY_TRY(c->room("egmj_slots", kBatch * 2 * kDiffSlots, &dslots));
+    AIY_TRY(c->room("egmj_status", 1, &dstatus));
     AIY_HIP(hipMemsetAsync(dstatus, 0, sizeof(int), c->st));
-    KsEgmArgs A{};
-    A.nk = (int)nk; A.nK = (int)nK; A.max_iter = (int)max_iter; A.k_grid = dkg; A.P = dP;
-    A.pairs = dpairs; A.beta = params[0]; A.k_min = params[3]; A.k_max = params[4]; A.tol = tol;
     auto slot = [&](int64_t g) { return ring + (size_t)(g % R) * n; };
     std::vector<unsigned long long> hs(kBatch * 2 * kDiffSlots);
     int64_t done = 0, stop = 0;
@@ -309,9 +313,8 @@ int ks_egm_solve_jacobi(double* k_opt, const double* k_grid, const double* K_gri
             AIY_TRY(launch_ks_egm_jacobi(A, slot(g - 1), slot(g),
                                          dslots + t * 2 * kDiffSlots, dstatus, c->st));
         }
-        AIY_HIP(hipMemcpyAsync(hs.data(), dslots, m * 2 * kDiffSlots * sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipMemcpyAsync(&status, dstatus, sizeof(int), hipMemcpyDeviceToHost, c->st));
+        AIY_TRY(c->down(hs.data(), dslots, m * 2 * kDiffSlots));
+        AIY_TRY(c->down(&status, dstatus, 1));
         AIY_HIP(hipStreamSynchronize(c->st));
         if (status) break;
         for (int64_t t = 0; t < m; ++t) {
@@ -323,11 +326,9 @@ int ks_egm_solve_jacobi(double* k_opt, const double* k_grid, const double* K_gri
         }
         if (!stop) done += m;
     }
-    if (status)
-        return fail(AIY_NON_FINITE, "an (s, K) pair had fewer than 2 valid EGM points "
-                                    "(griddedInterpolant needs two; Krusell_Smith_EGM.m:196)");
+    if (status) return no_egm_points();
     const int64_t g = stop ? stop : max_iter;
-    AIY_HIP(hipMemcpyAsync(k_opt, slot(g), n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(k_opt, slot(g), n));
     AIY_HIP(hipStreamSynchronize(c->st));
     *iters = g;
     *diff = d_last;

@@ -32,6 +32,27 @@ static int check_hist_params(const double* params) {
     return AIY_OK;
 }
 
+// What both tiers pass: the single tier adds thr (by value), the multi tier pol and thr_g.
+static HistArgs hist_args(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
+                          const double* k_opt, const double* x_grid, int64_t nx, const int8_t* zi,
+                          int64_t T, int64_t M, double* lam, double* K_ts, int64_t* slow) {
+    HistArgs A{};
+    A.nx = (int)nx;
+    A.nk = (int)nk;
+    A.nK = (int)nK;
+    A.T = (int)T;
+    A.M = (int)M;
+    A.k_grid = k_grid;
+    A.K_grid = K_grid;
+    A.x = x_grid;
+    A.k_opt = k_opt;
+    A.zi = zi;
+    A.lam = lam;
+    A.K_ts = K_ts;
+    A.slow = slow;
+    return A;
+}
+
 int hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
              const double* k_opt, const double* x_grid, int64_t nx, const double* params,
              const int8_t* zi, int64_t T, int64_t M, double* lam, double* K_ts, int64_t* slow,
@@ -45,21 +66,8 @@ int hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
         return fail(AIY_NO_DEVICE, "no HIP device visible");
     ShockArgs S{};
     shock_probs(params[5], params[6], S);
-    HistArgs A{};
-    A.nx = (int)nx;
-    A.nk = (int)nk;
-    A.nK = (int)nK;
-    A.T = (int)T;
-    A.M = (int)M;
+    HistArgs A = hist_args(nk, nK, k_grid, K_grid, k_opt, x_grid, nx, zi, T, M, lam, K_ts, slow);
     for (int q = 0; q < 8; ++q) A.thr[q] = S.thr[q];
-    A.k_grid = k_grid;
-    A.K_grid = K_grid;
-    A.x = x_grid;
-    A.k_opt = k_opt;
-    A.zi = zi;
-    A.lam = lam;
-    A.K_ts = K_ts;
-    A.slow = slow;
     return launch_ks_hist(A, st);
 }
 
@@ -100,23 +108,53 @@ static int hist_multi_dev(int64_t C, int64_t nk, int64_t nK, const double* k_gri
     AIY_HIP(hipMemcpyAsync(dthr, thr.data(), sizeof(double) * thr.size(), hipMemcpyHostToDevice, st));
     AIY_HIP(hipMemcpyAsync(dpol, pol, sizeof(int32_t) * M, hipMemcpyHostToDevice, st));
     AIY_HIP(hipStreamSynchronize(st));
-    HistArgs A{};
-    A.nx = (int)nx;
-    A.nk = (int)nk;
-    A.nK = (int)nK;
-    A.T = (int)T;
-    A.M = (int)M;
-    A.k_grid = k_grid;
-    A.K_grid = K_grid;
-    A.x = x_grid;
-    A.k_opt = k_opt;
-    A.zi = zi;
-    A.lam = lam;
-    A.K_ts = K_ts;
-    A.slow = slow;
+    HistArgs A = hist_args(nk, nK, k_grid, K_grid, k_opt, x_grid, nx, zi, T, M, lam, K_ts, slow);
     A.pol = dpol;
     A.thr_g = dthr;
     return launch_ks_hist(A, st);
+}
+
+// The host-tier body of ks_simulate_hist (pol == nullptr: one policy, C = 1, buffers ksh_*) and
+// ks_simulate_hist_multi (pol [M], C candidates, buffers kshm_*), behind their own checks: the
+// validated inputs up, the entry's device tier, lam, K_ts and the slow-period counts back.
+static int hist_host(int64_t C, const double* k_opt, const double* k_grid, const double* K_grid,
+                     int64_t nk, int64_t nK, const double* x_grid, int64_t nx,
+                     const double* params, const int32_t* pol, const std::vector<int8_t>& hz,
+                     int64_t T, int64_t M, double* lam, double* K_ts, int64_t* slow_periods) {
+    const size_t nko = (size_t)C * nk * nK * 4, nl = (size_t)2 * nx * M, nz = (size_t)T * M;
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
+    const std::string pre = pol ? "kshm_" : "ksh_";
+    auto nm = [&](const char* s) { return pre + s; };
+    double *dko, *dkg, *dKg, *dx, *dlam, *dKts;
+    int64_t* dslow;
+    int8_t* dz;
+    AIY_TRY(c->up(nm("kopt").c_str(), k_opt, nko, &dko));
+    AIY_TRY(c->up(nm("kg").c_str(), k_grid, nk, &dkg));
+    AIY_TRY(c->up(nm("Kg").c_str(), K_grid, C * nK, &dKg));
+    AIY_TRY(c->up(nm("x").c_str(), x_grid, nx, &dx));
+    AIY_TRY(c->up(nm("lam").c_str(), lam, nl, &dlam));
+    AIY_TRY(c->room(nm("Kts").c_str(), nz, &dKts));
+    AIY_TRY(c->room(nm("slow").c_str(), M, &dslow));
+    AIY_TRY(c->up(nm("zi").c_str(), hz.data(), nz, &dz));
+    if (pol) {
+        unsigned char* dscr;
+        AIY_TRY(c->room("kshm_scratch", hist_multi_scratch(C, M), &dscr));
+        AIY_TRY(hist_multi_dev(C, nk, nK, dkg, dKg, dko, dx, nx, params, pol, dz, T, M, dlam,
+                               dKts, dslow, dscr, c->st));
+    } else {
+        AIY_TRY(hist_dev(nk, nK, dkg, dKg, dko, dx, nx, params, dz, T, M, dlam, dKts, dslow,
+                         c->st));
+    }
+    AIY_TRY(c->down(lam, dlam, nl));
+    AIY_TRY(c->down(K_ts, dKts, nz));
+    std::vector<int64_t> hs(M);
+    AIY_TRY(c->down(hs.data(), dslow, M));
+    AIY_HIP(hipStreamSynchronize(c->st));
+    if (slow_periods)
+        for (int64_t m = 0; m < M; ++m) slow_periods[m] = hs[m];
+    return AIY_OK;
 }
 
 }  // namespace aiy
@@ -161,44 +199,10 @@ int ks_simulate_hist_multi(int64_t C, const double* k_opt, const double* k_grid,
         if (!std::isfinite(k_opt[q])) return fail(AIY_NON_FINITE, "non-finite k_opt");
     for (size_t q = 0; q < nl; ++q)
         if (!std::isfinite(lam[q])) return fail(AIY_NON_FINITE, "non-finite lam");
-    std::vector<int8_t> hz(nz);
-    for (size_t q = 0; q < nz; ++q) {
-        if (zi_shock[q] != 0 && zi_shock[q] != 1)
-            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
-        hz[q] = (int8_t)zi_shock[q];
-    }
-    std::lock_guard<std::mutex> lk(host_mutex());
-    HostCtx* c;
-    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
-    double *dko, *dkg, *dKg, *dx, *dlam, *dKts;
-    int64_t* dslow;
-    int8_t* dz;
-    void* dscr;
-    AIY_TRY(c->buf("kshm_kopt", sizeof(double) * nko, (void**)&dko));
-    AIY_TRY(c->buf("kshm_kg", sizeof(double) * nk, (void**)&dkg));
-    AIY_TRY(c->buf("kshm_Kg", sizeof(double) * C * nK, (void**)&dKg));
-    AIY_TRY(c->buf("kshm_x", sizeof(double) * nx, (void**)&dx));
-    AIY_TRY(c->buf("kshm_lam", sizeof(double) * nl, (void**)&dlam));
-    AIY_TRY(c->buf("kshm_Kts", sizeof(double) * nz, (void**)&dKts));
-    AIY_TRY(c->buf("kshm_slow", sizeof(int64_t) * M, (void**)&dslow));
-    AIY_TRY(c->buf("kshm_zi", nz, (void**)&dz));
-    AIY_TRY(c->buf("kshm_scratch", hist_multi_scratch(C, M), &dscr));
-    AIY_HIP(hipMemcpyAsync(dko, k_opt, sizeof(double) * nko, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, sizeof(double) * nk, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dKg, K_grid, sizeof(double) * C * nK, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dx, x_grid, sizeof(double) * nx, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dlam, lam, sizeof(double) * nl, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dz, hz.data(), nz, hipMemcpyHostToDevice, c->st));
-    AIY_TRY(hist_multi_dev(C, nk, nK, dkg, dKg, dko, dx, nx, params, policy_of_path, dz, T, M,
-                           dlam, dKts, dslow, dscr, c->st));
-    AIY_HIP(hipMemcpyAsync(lam, dlam, sizeof(double) * nl, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(K_ts, dKts, sizeof(double) * nz, hipMemcpyDeviceToHost, c->st));
-    std::vector<int64_t> hs(M);
-    AIY_HIP(hipMemcpyAsync(hs.data(), dslow, sizeof(int64_t) * M, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
-    if (slow_periods)
-        for (int64_t m = 0; m < M; ++m) slow_periods[m] = hs[m];
-    return AIY_OK;
+    std::vector<int8_t> hz;
+    AIY_TRY(zi_to_i8(zi_shock, nz, hz));
+    return hist_host(C, k_opt, k_grid, K_grid, nk, nK, x_grid, nx, params, policy_of_path, hz, T,
+                     M, lam, K_ts, slow_periods);
 }
 
 int ks_simulate_hist_dev(int64_t nk, int64_t nK, const double* k_grid, const double* K_grid,
@@ -226,41 +230,10 @@ int ks_simulate_hist(const double* k_opt, const double* k_grid, const double* K_
     for (size_t q = 0; q < nl; ++q)
         if (!std::isfinite(lam[q])) return fail(AIY_NON_FINITE, "non-finite lam");
     // T x M column-major: path m's chain is contiguous, the device tier's [M][T]
-    std::vector<int8_t> hz(nz);
-    for (size_t q = 0; q < nz; ++q) {
-        if (zi_shock[q] != 0 && zi_shock[q] != 1)
-            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
-        hz[q] = (int8_t)zi_shock[q];
-    }
-    std::lock_guard<std::mutex> lk(host_mutex());
-    HostCtx* c;
-    AIY_TRY(get_ctx(4 * nK, nk, 1, &c));
-    double *dko, *dkg, *dKg, *dx, *dlam, *dKts;
-    int64_t* dslow;
-    int8_t* dz;
-    AIY_TRY(c->buf("ksh_kopt", sizeof(double) * nko, (void**)&dko));
-    AIY_TRY(c->buf("ksh_kg", sizeof(double) * nk, (void**)&dkg));
-    AIY_TRY(c->buf("ksh_Kg", sizeof(double) * nK, (void**)&dKg));
-    AIY_TRY(c->buf("ksh_x", sizeof(double) * nx, (void**)&dx));
-    AIY_TRY(c->buf("ksh_lam", sizeof(double) * nl, (void**)&dlam));
-    AIY_TRY(c->buf("ksh_Kts", sizeof(double) * nz, (void**)&dKts));
-    AIY_TRY(c->buf("ksh_slow", sizeof(int64_t) * M, (void**)&dslow));
-    AIY_TRY(c->buf("ksh_zi", nz, (void**)&dz));
-    AIY_HIP(hipMemcpyAsync(dko, k_opt, sizeof(double) * nko, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, sizeof(double) * nk, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dKg, K_grid, sizeof(double) * nK, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dx, x_grid, sizeof(double) * nx, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dlam, lam, sizeof(double) * nl, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dz, hz.data(), nz, hipMemcpyHostToDevice, c->st));
-    AIY_TRY(hist_dev(nk, nK, dkg, dKg, dko, dx, nx, params, dz, T, M, dlam, dKts, dslow, c->st));
-    AIY_HIP(hipMemcpyAsync(lam, dlam, sizeof(double) * nl, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(K_ts, dKts, sizeof(double) * nz, hipMemcpyDeviceToHost, c->st));
-    std::vector<int64_t> hs(M);
-    AIY_HIP(hipMemcpyAsync(hs.data(), dslow, sizeof(int64_t) * M, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
-    if (slow_periods)
-        for (int64_t m = 0; m < M; ++m) slow_periods[m] = hs[m];
-    return AIY_OK;
+    std::vector<int8_t> hz;
+    AIY_TRY(zi_to_i8(zi_shock, nz, hz));
+    return hist_host(1, k_opt, k_grid, K_grid, nk, nK, x_grid, nx, params, nullptr, hz, T, M, lam,
+                     K_ts, slow_periods);
 }
 
 }  // extern "C"

@@ -86,30 +86,25 @@ static int ks_stage(HostCtx* c, const double* value, const double* k_opt, const 
     memcpy(&p, params, sizeof p);
     std::vector<KsSlice> sl;
     ks_slices(p, B, K_grid, (int)nK, sl);
-    size_t n = (size_t)nk * nK * 4, nb = n * sizeof(double);
-    AIY_TRY(c->buf("ks_kg", nk * sizeof(double), (void**)&D.kg));
-    AIY_TRY(c->buf("ks_kgt", 3 * nk * sizeof(double), (void**)&D.kgt));
-    AIY_TRY(c->buf("ks_P", 16 * sizeof(double), (void**)&D.P));
-    AIY_TRY(c->buf("ks_V", nb, (void**)&D.V));
-    AIY_TRY(c->buf("ks_V2", nb, (void**)&D.V2));
-    AIY_TRY(c->buf("ks_dV", nb, (void**)&D.dV));
-    AIY_TRY(c->buf("ks_dV2", nb, (void**)&D.dV2));
-    AIY_TRY(c->buf("ks_Vold", nb, (void**)&D.Vold));
-    AIY_TRY(c->buf("ks_kopt", nb, (void**)&D.kopt));
-    AIY_TRY(c->buf("ks_nfev", n * sizeof(int), (void**)&D.nfev));
-    AIY_TRY(c->buf("ks_seg", n * sizeof(int), (void**)&D.seg));
-    AIY_TRY(c->buf("ks_sl", sl.size() * sizeof(KsSlice), (void**)&D.sl));
-    AIY_TRY(c->buf("ks_out", sizeof(KsOut), (void**)&D.out));
-    AIY_TRY(c->buf("ks_slots", 2 * kDiffSlots * sizeof(unsigned long long), (void**)&D.slots));
+    const size_t n = (size_t)nk * nK * 4;
     double Pr[16];
-    for (int i = 0; i < 4; ++i)
-        for (int m = 0; m < 4; ++m) Pr[i * 4 + m] = P[i + m * 4];
-    AIY_HIP(hipMemcpyAsync(D.kg, k_grid, nk * sizeof(double), hipMemcpyHostToDevice, c->st));
+    p_rows(P, Pr);
+    AIY_TRY(c->up("ks_kg", k_grid, nk, &D.kg));
+    AIY_TRY(c->room("ks_kgt", 3 * nk, &D.kgt));
     AIY_TRY(launch_ks_grid_tables(D.kg, (int)nk, D.kgt, c->st));
-    AIY_HIP(hipMemcpyAsync(D.P, Pr, sizeof Pr, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(D.V, value, nb, hipMemcpyHostToDevice, c->st));
-    if (k_opt) AIY_HIP(hipMemcpyAsync(D.kopt, k_opt, nb, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(D.sl, sl.data(), sl.size() * sizeof(KsSlice), hipMemcpyHostToDevice, c->st));
+    AIY_TRY(c->up("ks_P", Pr, 16, &D.P));
+    AIY_TRY(c->up("ks_V", value, n, &D.V));
+    AIY_TRY(c->room("ks_V2", n, &D.V2));
+    AIY_TRY(c->room("ks_dV", n, &D.dV));
+    AIY_TRY(c->room("ks_dV2", n, &D.dV2));
+    AIY_TRY(c->room("ks_Vold", n, &D.Vold));
+    if (k_opt) AIY_TRY(c->up("ks_kopt", k_opt, n, &D.kopt));
+    else AIY_TRY(c->room("ks_kopt", n, &D.kopt));
+    AIY_TRY(c->room("ks_nfev", n, &D.nfev));
+    AIY_TRY(c->room("ks_seg", n, &D.seg));
+    AIY_TRY(c->up("ks_sl", sl.data(), sl.size(), &D.sl));
+    AIY_TRY(c->room("ks_out", 1, &D.out));
+    AIY_TRY(c->room("ks_slots", 2 * kDiffSlots, &D.slots));
     AIY_HIP(hipStreamSynchronize(c->st));
     A = KsArgs{};
     A.nk = (int)nk; A.nK = (int)nK; A.node0 = 0; A.n_local = (int)n;
@@ -121,8 +116,7 @@ static int ks_stage(HostCtx* c, const double* value, const double* k_opt, const 
 
 static int ks_read_slots(HostCtx* c, const unsigned long long* slots, double* d) {
     std::vector<unsigned long long> h(2 * kDiffSlots);
-    AIY_HIP(hipMemcpyAsync(h.data(), slots, h.size() * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(h.data(), slots, h.size()));
     AIY_HIP(hipStreamSynchronize(c->st));
     *d = fold_slots_host(h.data());
     return AIY_OK;
@@ -147,8 +141,8 @@ int ks_policy_improve(const double* value, const double* k_grid, const double* K
     AIY_TRY(launch_ks_slopes(A, D.V, D.dV, c->st));
     AIY_TRY(launch_ks_improve(A, D.V, D.dV, D.kopt, D.nfev, c->st));
     size_t n = (size_t)nk * nK * 4;
-    AIY_HIP(hipMemcpyAsync(k_opt, D.kopt, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    if (nfev) AIY_HIP(hipMemcpyAsync(nfev, D.nfev, n * sizeof(int), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(k_opt, D.kopt, n));
+    if (nfev) AIY_TRY(c->down(nfev, D.nfev, n));
     AIY_HIP(hipStreamSynchronize(c->st));
     return AIY_OK;
 }
@@ -173,7 +167,7 @@ int ks_howard(double* value, const double* k_opt, const double* k_grid, const do
         std::swap(dcur, dnxt);
     }
     size_t n = (size_t)nk * nK * 4;
-    AIY_HIP(hipMemcpyAsync(value, cur, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(value, cur, n));
     AIY_HIP(hipStreamSynchronize(c->st));
     return AIY_OK;
 }
@@ -204,9 +198,9 @@ int ks_vfi_solve(double* value, double* k_opt, const double* k_grid, const doubl
     if (ks_fused_fits((int)nk, (int)nK)) {
         AIY_TRY(launch_ks_fused(A, D.V, D.kopt, nullptr, D.out, c->st));
         KsOut o;
-        AIY_HIP(hipMemcpyAsync(&o, D.out, sizeof o, hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipMemcpyAsync(value, D.V, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipMemcpyAsync(k_opt, D.kopt, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+        AIY_TRY(c->down(&o, D.out, 1));
+        AIY_TRY(c->down(value, D.V, n));
+        AIY_TRY(c->down(k_opt, D.kopt, n));
         AIY_HIP(hipStreamSynchronize(c->st));
         *iters = o.iters;
         *rel_diff = o.rel;
@@ -237,8 +231,8 @@ int ks_vfi_solve(double* value, double* k_opt, const double* k_grid, const doubl
         if (rel < tol) break;
     }
     if (it > max_vfi) it = max_vfi;
-    AIY_HIP(hipMemcpyAsync(value, cur, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(k_opt, D.kopt, n * sizeof(double), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(value, cur, n));
+    AIY_TRY(c->down(k_opt, D.kopt, n));
     AIY_HIP(hipStreamSynchronize(c->st));
     *iters = it;
     *rel_diff = rel;

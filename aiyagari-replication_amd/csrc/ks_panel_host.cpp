@@ -38,6 +38,17 @@ void shock_probs(double ug, double ub, ShockArgs& A) {
     }
 }
 
+// MATLAB's lookup (:227-231) maps only z in z_grid; other codes error
+int zi_to_i8(const double* zi_shock, size_t n, std::vector<int8_t>& out) {
+    out.resize(n);
+    for (size_t q = 0; q < n; ++q) {
+        if (zi_shock[q] != 0 && zi_shock[q] != 1)
+            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
+        out[q] = (int8_t)zi_shock[q];
+    }
+    return AIY_OK;
+}
+
 static int check_panel_shape(int64_t T, int64_t pop) {
     if (T < 1 || T > (1ll << 30)) return fail(AIY_BAD_SHAPE, "T must be in [1, 2^30]");
     if (pop < 1 || pop > (1ll << 31) - 1) return fail(AIY_BAD_SHAPE, "population must be in [1, 2^31)");
@@ -129,15 +140,14 @@ int ks_shocks(int64_t T, int64_t population, const double* uniforms, const doubl
     const int64_t nU = ks_shock_draws(T, population);
     double* dU;
     int8_t *dz, *de;
-    AIY_TRY(c->buf("ksp_U", sizeof(double) * nU, (void**)&dU));
-    AIY_TRY(c->buf("ksp_zi", (size_t)T, (void**)&dz));
-    AIY_TRY(c->buf("ksp_eps", (size_t)T * population, (void**)&de));
-    AIY_HIP(hipMemcpyAsync(dU, uniforms, sizeof(double) * nU, hipMemcpyHostToDevice, c->st));
+    AIY_TRY(c->up("ksp_U", uniforms, nU, &dU));
+    AIY_TRY(c->room("ksp_zi", T, &dz));
+    AIY_TRY(c->room("ksp_eps", (size_t)T * population, &de));
     // MATLAB epsi_shock is T x population column-major: (t, i) at t + T*i
     AIY_TRY(shocks_dev(T, population, dU, params, dz, de, 1, T, c->st));
     std::vector<int8_t> hz(T), he((size_t)T * population);
-    AIY_HIP(hipMemcpyAsync(hz.data(), dz, (size_t)T, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(he.data(), de, he.size(), hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(hz.data(), dz, T));
+    AIY_TRY(c->down(he.data(), de, he.size()));
     AIY_HIP(hipStreamSynchronize(c->st));
     for (int64_t t = 0; t < T; ++t) zi_shock[t] = hz[t];           // after :68 (0 good)
     for (size_t q = 0; q < he.size(); ++q) epsi_shock[q] = he[q] + 1;  // 1 employed, 2 not
@@ -155,12 +165,8 @@ int ks_simulate_capital(const double* k_opt, const double* k_grid, const double*
     AIY_TRY(check_grid_strict(k_grid, nk));  // griddedInterpolant rejects repeated points
     AIY_TRY(check_grid_strict(K_grid, nK));
     // MATLAB's lookup (:227-231) maps only z in z_grid and eps in eps_grid; other codes error
-    std::vector<int8_t> hz(T), he((size_t)T * population);
-    for (int64_t t = 0; t < T; ++t) {
-        if (zi_shock[t] != 0 && zi_shock[t] != 1)
-            return fail(AIY_BAD_ARG, "zi_shock must hold 0 (good) or 1 (bad)");
-        hz[t] = (int8_t)zi_shock[t];
-    }
+    std::vector<int8_t> hz, he((size_t)T * population);
+    AIY_TRY(zi_to_i8(zi_shock, T, hz));
     for (size_t q = 0; q < he.size(); ++q) {
         if (epsi_shock[q] != 1 && epsi_shock[q] != 2)
             return fail(AIY_BAD_ARG, "epsi_shock must hold 1 (employed) or 2 (unemployed)");
@@ -174,23 +180,17 @@ int ks_simulate_capital(const double* k_opt, const double* k_grid, const double*
     const size_t nko = (size_t)nk * nK * 4;
     double *dko, *dkg, *dKg, *dkp, *dKts, *dpart;
     int8_t *dz, *de;
-    AIY_TRY(c->buf("ksp_kopt", sizeof(double) * nko, (void**)&dko));
-    AIY_TRY(c->buf("ksp_kg", sizeof(double) * nk, (void**)&dkg));
-    AIY_TRY(c->buf("ksp_Kg", sizeof(double) * nK, (void**)&dKg));
-    AIY_TRY(c->buf("ksp_kpop", sizeof(double) * population, (void**)&dkp));
-    AIY_TRY(c->buf("ksp_Kts", sizeof(double) * T, (void**)&dKts));
-    AIY_TRY(c->buf("ksp_part", (size_t)ks_panel_scratch_bytes(population), (void**)&dpart));
-    AIY_TRY(c->buf("ksp_zi", (size_t)T, (void**)&dz));
-    AIY_TRY(c->buf("ksp_eps", he.size(), (void**)&de));
-    AIY_HIP(hipMemcpyAsync(dko, k_opt, sizeof(double) * nko, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dkg, k_grid, sizeof(double) * nk, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dKg, K_grid, sizeof(double) * nK, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dkp, k_population, sizeof(double) * population, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dz, hz.data(), (size_t)T, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(de, he.data(), he.size(), hipMemcpyHostToDevice, c->st));
+    AIY_TRY(c->up("ksp_kopt", k_opt, nko, &dko));
+    AIY_TRY(c->up("ksp_kg", k_grid, nk, &dkg));
+    AIY_TRY(c->up("ksp_Kg", K_grid, nK, &dKg));
+    AIY_TRY(c->up("ksp_kpop", k_population, population, &dkp));
+    AIY_TRY(c->room("ksp_Kts", T, &dKts));
+    AIY_TRY(c->room("ksp_part", 2 * (size_t)panel_blocks(population), &dpart));
+    AIY_TRY(c->up("ksp_zi", hz.data(), T, &dz));
+    AIY_TRY(c->up("ksp_eps", he.data(), he.size(), &de));
     AIY_TRY(panel_dev(nk, nK, dkg, dKg, dko, T, population, dz, de, 1, T, dkp, dKts, dpart, c->st));
-    AIY_HIP(hipMemcpyAsync(k_population, dkp, sizeof(double) * population, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(K_ts, dKts, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(k_population, dkp, population));
+    AIY_TRY(c->down(K_ts, dKts, T));
     AIY_HIP(hipStreamSynchronize(c->st));
     return AIY_OK;
 }

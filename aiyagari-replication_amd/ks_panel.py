@@ -12,17 +12,15 @@ import ctypes as C
 
 import numpy as np
 
+from . import calibration
 from ._capi import check, i64, lib, ptr, stream_handle
+from .ge import matlab_rand  # noqa: F401  (the fresh-session stream; exported from here too)
+from .ks import _per_candidate, ks_egm_solve, ks_egm_solve_batch_dev, ks_params, ks_vfi_solve
 
 
 def shock_draws(T: int, population: int) -> int:
     """Uniforms consumed by :57-94: T-1 aggregate, `population` initial, (T-1)*population."""
     return (T - 1) + population + (T - 1) * population
-
-
-def matlab_rand(n: int, seed: int = 5489) -> np.ndarray:
-    """A fresh MATLAB session's first n `rand` values (mt19937ar, genrand_res53)."""
-    return np.random.RandomState(seed).random_sample(n)
 
 
 def ks_shocks(T, population, uniforms, params):
@@ -150,6 +148,23 @@ def _hist_shapes(k_opt, k_grid, K_grid, x_grid):
     return nk, nK, x_grid.size
 
 
+def _paths_2d(zi_paths, dtype=None):
+    zi = np.asarray(zi_paths, dtype)
+    return zi[:, None] if zi.ndim == 1 else zi
+
+
+def _host_paths(zi_paths):
+    """The host tier's zi_shock: (T, M) float64 column-major; with T and M."""
+    zi = _paths_2d(zi_paths, np.float64)
+    return (np.asfortranarray(zi),) + zi.shape
+
+
+def _host_state(lam0, T, M, nx):
+    """The host tier's lam (M, 2, nx) from lam0, and its outputs K_ts (T, M) and slow (M,)."""
+    lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (M, 2, nx)), order="C")
+    return lam, np.empty((T, M), order="F"), np.zeros(M, np.int64)
+
+
 def ks_simulate_hist(k_opt, k_grid, K_grid, x_grid, zi_paths, lam0, params):
     """The histogram simulation of the capital path through the host tier.  k_opt k x K x 4;
     zi_paths (T, M) in {0, 1}; lam0 (M, 2, nx) or (2, nx) (every path starts from it).
@@ -159,48 +174,55 @@ def ks_simulate_hist(k_opt, k_grid, K_grid, x_grid, zi_paths, lam0, params):
     Kg = np.ascontiguousarray(K_grid, np.float64)
     x = np.ascontiguousarray(x_grid, np.float64)
     nk, nK, nx = _hist_shapes(ko, kg, Kg, x)
-    zi = np.asarray(zi_paths, np.float64)
-    zi = zi[:, None] if zi.ndim == 1 else zi
-    T, M = zi.shape
-    zi = np.asfortranarray(zi)
-    lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (M, 2, nx)), order="C")
+    zi, T, M = _host_paths(zi_paths)
+    lam, K_ts, slow = _host_state(lam0, T, M, nx)
     prm = np.ascontiguousarray(params, np.float64)
     if prm.size != 13:
         raise ValueError("params must hold the 13 KS doubles")
-    K_ts = np.empty((T, M), order="F")
-    slow = np.zeros(M, np.int64)
     check(lib().ks_simulate_hist(ptr(ko), ptr(kg), ptr(Kg), i64(nk), i64(nK), ptr(x), i64(nx),
                                  ptr(prm), ptr(zi), i64(T), i64(M), ptr(lam), ptr(K_ts),
                                  ptr(slow)))
     return K_ts, lam, slow
 
 
-class HistSim:
-    """Device-resident histogram simulation: grids, the M shock paths and the distributions stay
-    in HBM across calls.  zi_paths (T, M) host array in {0, 1}; lam0 (M, 2, nx) or (2, nx).
-    `lam` persists across calls like PanelSim's population; set_lam restarts it."""
+class _HistState:
+    """What HistSim and HistSimMulti keep in HBM across calls: k_grid, x_grid, the M shock paths
+    (int8 [M][T]), the distributions lam [M][2][nx], K_ts [M][T] and the slow-period counts."""
 
-    def __init__(self, k_grid, K_grid, x_grid, zi_paths, lam0, params, device="cuda"):
+    def __init__(self, k_grid, x_grid, zi_paths, lam0, device, params=None):
         import torch
         dev = torch.device(device)
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.k_grid = torch.as_tensor(np.ascontiguousarray(k_grid, np.float64), **f64)
-        self.K_grid = torch.as_tensor(np.ascontiguousarray(K_grid, np.float64), **f64)
-        self.x_grid = torch.as_tensor(np.ascontiguousarray(x_grid, np.float64), **f64)
-        zi = np.asarray(zi_paths)
-        zi = zi[:, None] if zi.ndim == 1 else zi
+        self._f64 = dict(dtype=torch.float64, device=dev)
+        self.k_grid = self._grid(k_grid)
+        self.x_grid = self._grid(x_grid)
+        zi = _paths_2d(zi_paths)
         if not np.all((zi == 0) | (zi == 1)):
             raise ValueError("zi_paths must hold 0 (good) or 1 (bad)")
         self.T, self.M = zi.shape
         self.nx = self.x_grid.numel()
         self.zi = torch.as_tensor(np.ascontiguousarray(zi.T.astype(np.int8)), device=dev)
-        self.params = np.ascontiguousarray(params, np.float64)
-        if self.params.size != 13:
-            raise ValueError("params must hold the 13 KS doubles")
-        self.lam = torch.empty((self.M, 2, self.nx), **f64)
+        if params is not None:
+            self.params = np.ascontiguousarray(params, np.float64)
+            if self.params.size != 13:
+                raise ValueError("params must hold the 13 KS doubles")
+        self.lam = torch.empty((self.M, 2, self.nx), **self._f64)
         self.set_lam(lam0)
-        self.K_ts = torch.empty((self.M, self.T), **f64)
+        self.K_ts = torch.empty((self.M, self.T), **self._f64)
         self.slow = torch.zeros(self.M, dtype=torch.int64, device=dev)
+
+    def _grid(self, g):
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(g, np.float64), **self._f64)
+
+
+class HistSim(_HistState):
+    """Device-resident histogram simulation: grids, the M shock paths and the distributions stay
+    in HBM across calls.  zi_paths (T, M) host array in {0, 1}; lam0 (M, 2, nx) or (2, nx).
+    `lam` persists across calls like PanelSim's population; set_lam restarts it."""
+
+    def __init__(self, k_grid, K_grid, x_grid, zi_paths, lam0, params, device="cuda"):
+        super().__init__(k_grid, x_grid, zi_paths, lam0, device, params)
+        self.K_grid = self._grid(K_grid)
 
     def set_lam(self, lam0):
         import torch
@@ -224,7 +246,6 @@ class HistSim:
 def _multi_shapes(k_opt, k_grid, K_grid, params, policy_of_path, M):
     """Candidate-major host inputs of the one-policy-per-path simulation: k_opt (C, nk, nK, 4),
     K_grid (C, nK) and params (C, 13) (one candidate's shape broadcasts), policy_of_path (M,)."""
-    from .ks import _per_candidate
     ko = np.asarray(k_opt, np.float64)
     if ko.ndim != 4 or ko.shape[3] != 4:
         raise ValueError("k_opt must be (C, k_size, K_size, 4)")
@@ -246,23 +267,18 @@ def ks_simulate_hist_multi(k_opt, k_grid, K_grid, x_grid, zi_paths, lam0, params
     policy_of_path[m].  Returns (K_ts (T, M), lam (M, 2, nx), slow_periods (M,))."""
     kg = np.ascontiguousarray(k_grid, np.float64)
     x = np.ascontiguousarray(x_grid, np.float64)
-    zi = np.asarray(zi_paths, np.float64)
-    zi = zi[:, None] if zi.ndim == 1 else zi
-    T, M = zi.shape
-    zi = np.asfortranarray(zi)
+    zi, T, M = _host_paths(zi_paths)
     ko, Kg, prm, pol, C_, nk, nK = _multi_shapes(k_opt, kg, K_grid, params, policy_of_path, M)
     kd = np.ascontiguousarray(ko.transpose(0, 3, 2, 1))    # each block k x K x 4 column-major
     nx = x.size
-    lam = np.array(np.broadcast_to(np.asarray(lam0, np.float64), (M, 2, nx)), order="C")
-    K_ts = np.empty((T, M), order="F")
-    slow = np.zeros(M, np.int64)
+    lam, K_ts, slow = _host_state(lam0, T, M, nx)
     check(lib().ks_simulate_hist_multi(i64(C_), ptr(kd), ptr(kg), ptr(Kg), i64(nk), i64(nK),
                                        ptr(x), i64(nx), ptr(prm), ptr(pol), ptr(zi), i64(T),
                                        i64(M), ptr(lam), ptr(K_ts), ptr(slow)))
     return K_ts, lam, slow
 
 
-class HistSimMulti:
+class HistSimMulti(_HistState):
     """Device-resident histogram simulation with one policy per path: k_grid, x_grid, the M
     shock paths and the distributions stay in HBM across calls; the candidates (policies, their
     K_grid rows and params) and policy_of_path come with each call.  zi_paths (T, M) host array
@@ -270,22 +286,7 @@ class HistSimMulti:
     call with fewer than M entries in policy_of_path runs the first len(policy_of_path) paths."""
 
     def __init__(self, k_grid, x_grid, zi_paths, lam0, device="cuda"):
-        import torch
-        dev = torch.device(device)
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.k_grid = torch.as_tensor(np.ascontiguousarray(k_grid, np.float64), **f64)
-        self.x_grid = torch.as_tensor(np.ascontiguousarray(x_grid, np.float64), **f64)
-        zi = np.asarray(zi_paths)
-        zi = zi[:, None] if zi.ndim == 1 else zi
-        if not np.all((zi == 0) | (zi == 1)):
-            raise ValueError("zi_paths must hold 0 (good) or 1 (bad)")
-        self.T, self.M = zi.shape
-        self.nx = self.x_grid.numel()
-        self.zi = torch.as_tensor(np.ascontiguousarray(zi.T.astype(np.int8)), device=dev)
-        self.lam = torch.empty((self.M, 2, self.nx), **f64)
-        self.set_lam(lam0)
-        self.K_ts = torch.empty((self.M, self.T), **f64)
-        self.slow = torch.zeros(self.M, dtype=torch.int64, device=dev)
+        super().__init__(k_grid, x_grid, zi_paths, lam0, device)
         self.scratch = None
 
     def set_lam(self, lam0):
@@ -306,7 +307,6 @@ class HistSimMulti:
         C_, nS, nK, nk = k_opt.shape
         if nS != 4 or nk != self.k_grid.numel():
             raise ValueError("k_opt must be [C][4][K_size][numel(k_grid)]")
-        from .ks import _per_candidate
         if not hasattr(K_grid, "data_ptr"):
             K_grid = torch.as_tensor(np.array(_per_candidate(K_grid, C_, (nK,), "K_grid"),
                                               order="C"), device=self.lam.device)
@@ -339,24 +339,9 @@ class HistSimMulti:
 def alm_regress(K_ts, zi_shock, T_discard=100):
     """Krusell_Smith_VFI.m:252-285: OLS of log K(t+1) on [1, log K(t)] per aggregate state,
     t = T_discard..T-1.  Host-side (4 coefficients; SURVEY C13 is out of the kernel scope).
-    Returns (B_new, R2_good, R2_bad)."""
-    K_ts = np.asarray(K_ts, np.float64)
-    zi = np.asarray(zi_shock)
-    ts = np.arange(T_discard - 1, K_ts.size - 1)
-    B = np.zeros(4)
-    R2 = [0.0, 0.0]
-    for g in (0, 1):
-        sel = ts[zi[ts] == g]
-        if sel.size == 0:
-            continue
-        X = np.stack([np.ones(sel.size), np.log(K_ts[sel])], 1)
-        Y = np.log(K_ts[sel + 1])
-        Q, R = np.linalg.qr(X)
-        b = np.linalg.solve(R, Q.T @ Y)
-        B[2 * g:2 * g + 2] = b
-        res = Y - X @ b
-        R2[g] = 1 - np.sum(res ** 2) / np.sum((Y - Y.mean()) ** 2)
-    return B, R2[0], R2[1]
+    Returns (B_new, R2_good, R2_bad).  It is alm_regress_paths on the one path."""
+    return alm_regress_paths(np.asarray(K_ts, np.float64).ravel(), np.asarray(zi_shock).ravel(),
+                             T_discard)
 
 
 def alm_regress_paths(K_ts, zi, T_discard=100):
@@ -389,6 +374,77 @@ def alm_regress_paths(K_ts, zi, T_discard=100):
     return B, R2[0], R2[1]
 
 
+def _alm_step(B, B_new, tol_B, update_B):
+    """One economy's stop test and damped update (:286-295): (diff_B, done, the next B)."""
+    diff_B = float(np.max(np.abs(B_new - B)))                                  # :286
+    if diff_B < tol_B:
+        return diff_B, True, B
+    return diff_B, False, update_B * B_new + (1 - update_B) * B                 # :295
+
+
+def _alm_loop(solve, simulate, regress, B0, max_iter_B, tol_B, update_B, log):
+    """The outer loop of :138-296: solve(B) -> k_opt, simulate(k_opt) -> K_ts, regress(K_ts) ->
+    (B_new, R2_good, R2_bad), until max |B_new - B| < tol_B.  Returns (B, B_history, R2, K_ts)."""
+    B, hist, R2, K_ts = B0, [], (0.0, 0.0), None
+    for it in range(max_iter_B):
+        K_ts = simulate(solve(B))
+        B_new, r2g, r2b = regress(K_ts)
+        R2 = (r2g, r2b)
+        diff_B, done, B = _alm_step(B, B_new, tol_B, update_B)
+        hist.append(B_new.copy())
+        if log:
+            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
+        if done:
+            break
+    return B, hist, R2, K_ts
+
+
+def _check_simulate(simulate):
+    if simulate not in ("panel", "histogram"):
+        raise ValueError(f'simulate must be "panel" or "histogram", got {simulate!r}')
+
+
+def _alm_simulation(simulate, prm, kg, Kg, T, population, uniforms, n_paths, nx):
+    """The simulation step of an ALM loop: (run(k_opt) -> K_ts, zi, extra).  "panel": the agent
+    panel, the population persisting across calls (:101).  "histogram": HistSim on n_paths
+    paths; between calls the capital marginal of the last distribution is carried and re-split
+    (1 - ug, ug) over employment, the analogue of k_population persisting while epsi_shock
+    restarts at its first row.  `extra` holds what only the histogram returns (slow_periods,
+    filled by each run, and x_grid)."""
+    if simulate == "histogram":
+        import torch
+        ug = float(prm[5])
+        U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
+        zi = zi_paths(T, n_paths, U, prm)
+        x = hist_grid(nx, float(prm[3]), float(prm[4]))
+        sim = HistSim(kg, Kg, x, zi, hist_start(x, Kg[0], ug), prm)
+        extra = dict(slow_periods=None, x_grid=x)
+
+        def run(k_opt):
+            ko_dev = torch.as_tensor(np.ascontiguousarray(k_opt.transpose(2, 1, 0)),
+                                     device=sim.lam.device)
+            K_ts = sim(ko_dev).cpu().numpy().T
+            extra["slow_periods"] = sim.slow.cpu().numpy()
+            sim.set_lam(hist_carry(sim.lam.cpu().numpy(), ug))
+            return K_ts
+    else:
+        U = matlab_rand(shock_draws(T, population)) if uniforms is None else uniforms
+        zi, eps = ks_shocks(T, population, U, prm)
+        pop = [np.full(population, Kg[0])]                                      # :101
+        extra = {}
+
+        def run(k_opt):
+            K_ts, pop[0] = ks_simulate_capital(k_opt, kg, Kg, zi, eps, pop[0])
+            return K_ts
+    return run, zi, extra
+
+
+def _alm_start(kg, K_size):
+    """k_opt = 0.9 k (:97) and the identity law of motion (:99)."""
+    return (0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2),
+            np.array([0.0, 1.0, 0.0, 1.0]))
+
+
 def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B=100, tol_B=1e-6,
                       update_B=0.3, howard_steps=50, tol_vfi=1e-6, max_vfi=10000, T_discard=100,
                       uniforms=None, n_devices=1, log=None, simulate="panel", n_paths=1,
@@ -400,88 +456,26 @@ def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
     n_paths shock paths over an nx-point grid instead of the agent panel, and the regression is
     pooled over the paths (alm_regress_paths); K_ts and zi are then (T, n_paths).  `uniforms`
     then holds n_paths * (T - 1) aggregate draws."""
-    from . import calibration
-    from .ks import ks_params, ks_vfi_solve
-    if simulate not in ("panel", "histogram"):
-        raise ValueError(f'simulate must be "panel" or "histogram", got {simulate!r}')
+    _check_simulate(simulate)
     prm = ks_params()
     kg, Kg, P, V0 = calibration.krusell_smith(k_size=k_size, K_size=K_size)
-    if simulate == "histogram":
-        return _krusell_smith_vfi_hist(prm, kg, Kg, P, V0, T, max_iter_B, tol_B, update_B,
-                                       howard_steps, tol_vfi, max_vfi, T_discard, uniforms,
-                                       n_devices, log, n_paths, nx)
-    U = matlab_rand(shock_draws(T, population)) if uniforms is None else uniforms
-    zi, eps = ks_shocks(T, population, U, prm)
-    value = V0
-    k_opt = 0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2)    # :97
-    B = np.array([0.0, 1.0, 0.0, 1.0])                                          # :99
-    k_pop = np.full(population, Kg[0])                                          # :101
-    hist, R2, K_ts, vfi_iters = [], (0.0, 0.0), None, []
-    for it in range(max_iter_B):
-        R = ks_vfi_solve(value, k_opt, kg, Kg, B, P, prm, howard_steps=howard_steps, tol=tol_vfi,
-                         max_vfi=max_vfi, n_devices=n_devices)
-        value, k_opt = R["value"], R["k_opt"]
-        vfi_iters.append(R["iters"])
-        K_ts, k_pop = ks_simulate_capital(k_opt, kg, Kg, zi, eps, k_pop)
-        B_new, r2g, r2b = alm_regress(K_ts, zi, T_discard)
-        R2 = (r2g, r2b)
-        diff_B = float(np.max(np.abs(B_new - B)))                              # :286
-        hist.append(B_new.copy())
-        if log:
-            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
-        if diff_B < tol_B:
-            break
-        B = update_B * B_new + (1 - update_B) * B                                # :295
-    return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, value=value, k_opt=k_opt,
-                vfi_iters=vfi_iters, zi=zi)
+    run, zi, extra = _alm_simulation(simulate, prm, kg, Kg, T, population, uniforms, n_paths, nx)
+    k_opt, B0 = _alm_start(kg, K_size)
+    st = dict(value=V0, k_opt=k_opt, vfi_iters=[])
 
-
-def _krusell_smith_vfi_hist(prm, kg, Kg, P, V0, T, max_iter_B, tol_B, update_B, howard_steps,
-                            tol_vfi, max_vfi, T_discard, uniforms, n_devices, log, n_paths, nx):
-    """krusell_smith_vfi's loop with the histogram simulation in place of the panel.  Between
-    ALM iterations the capital marginal of the last distribution is carried and re-split
-    (1 - ug, ug) over employment — the analogue of k_population persisting (:101) while
-    epsi_shock restarts at its first row."""
-    import torch
-    from .ks import ks_vfi_solve
-    k_size, K_size = kg.size, Kg.size
-    ug = float(prm[5])
-    U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
-    zi = zi_paths(T, n_paths, U, prm)
-    x = hist_grid(nx, float(prm[3]), float(prm[4]))
-    sim = HistSim(kg, Kg, x, zi, hist_start(x, Kg[0], ug), prm)
-    value = V0
-    k_opt = 0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2)    # :97
-    B = np.array([0.0, 1.0, 0.0, 1.0])                                          # :99
-    hist, R2, K_ts, vfi_iters, slow = [], (0.0, 0.0), None, [], None
-    for it in range(max_iter_B):
-        R = ks_vfi_solve(value, k_opt, kg, Kg, B, P, prm, howard_steps=howard_steps, tol=tol_vfi,
-                         max_vfi=max_vfi, n_devices=n_devices)
-        value, k_opt = R["value"], R["k_opt"]
-        vfi_iters.append(R["iters"])
-        ko_dev = torch.as_tensor(np.ascontiguousarray(k_opt.transpose(2, 1, 0)),
-                                 device=sim.lam.device)
-        K_ts = sim(ko_dev).cpu().numpy().T
-        slow = sim.slow.cpu().numpy()
-        lam = sim.lam.cpu().numpy()
-        sim.set_lam(hist_carry(lam, ug))
-        B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
-        R2 = (r2g, r2b)
-        diff_B = float(np.max(np.abs(B_new - B)))                              # :286
-        hist.append(B_new.copy())
-        if log:
-            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
-        if diff_B < tol_B:
-            break
-        B = update_B * B_new + (1 - update_B) * B                                # :295
-    return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, value=value, k_opt=k_opt,
-                vfi_iters=vfi_iters, zi=zi, slow_periods=slow, x_grid=x)
+    def solve(B):
+        R = ks_vfi_solve(st["value"], st["k_opt"], kg, Kg, B, P, prm, howard_steps=howard_steps,
+                         tol=tol_vfi, max_vfi=max_vfi, n_devices=n_devices)
+        st.update(value=R["value"], k_opt=R["k_opt"])
+        st["vfi_iters"].append(R["iters"])
+        return R["k_opt"]
+    B, hist, R2, K_ts = _alm_loop(solve, run, lambda K: alm_regress_paths(K, zi, T_discard), B0,
+                                  max_iter_B, tol_B, update_B, log)
+    return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, **st, zi=zi, **extra)
 
 
 def _egm_economy(k_size, K_size, economy):
     """(params, k_grid, K_grid, P) of one economy: ks_params keywords plus K_min and K_max."""
-    from . import calibration
-    from .ks import ks_params
     eco = dict(economy)
     K_min, K_max = eco.pop("K_min", 30.0), eco.pop("K_max", 50.0)
     prm = ks_params(**eco)
@@ -502,51 +496,20 @@ def krusell_smith_egm(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
     simulate="histogram": the histogram simulation on n_paths shock paths over an nx-point grid
     in place of the panel, as krusell_smith_vfi's; K_ts and zi are then (T, n_paths) and
     `uniforms` holds n_paths * (T - 1) aggregate draws."""
-    from .ks import ks_egm_solve
-    if simulate not in ("panel", "histogram"):
-        raise ValueError(f'simulate must be "panel" or "histogram", got {simulate!r}')
+    _check_simulate(simulate)
     prm, kg, Kg, P = _egm_economy(k_size, K_size, economy)
-    hist_sim = simulate == "histogram"
-    if hist_sim:
-        import torch
-        ug = float(prm[5])
-        U = matlab_rand(n_paths * (T - 1)) if uniforms is None else uniforms
-        zi = zi_paths(T, n_paths, U, prm)
-        x = hist_grid(nx, float(prm[3]), float(prm[4]))
-        sim = HistSim(kg, Kg, x, zi, hist_start(x, Kg[0], ug), prm)
-    else:
-        U = matlab_rand(shock_draws(T, population)) if uniforms is None else uniforms
-        zi, eps = ks_shocks(T, population, U, prm)
-        k_pop = np.full(population, Kg[0])                                      # :99
-    k_opt = 0.9 * np.repeat(np.repeat(kg[:, None, None], K_size, 1), 4, 2)    # :96
-    B = np.array([0.0, 1.0, 0.0, 1.0])                                          # :97
-    hist, R2, K_ts, egm_iters, slow = [], (0.0, 0.0), None, [], None
-    for it in range(max_iter_B):
-        R = ks_egm_solve(k_opt, kg, Kg, B, P, prm, tol=tol_egm, max_iter=max_egm)
-        k_opt = R["k_opt"]
-        egm_iters.append(R["iters"])
-        if hist_sim:
-            ko_dev = torch.as_tensor(np.ascontiguousarray(k_opt.transpose(2, 1, 0)),
-                                     device=sim.lam.device)
-            K_ts = sim(ko_dev).cpu().numpy().T
-            slow = sim.slow.cpu().numpy()
-            sim.set_lam(hist_carry(sim.lam.cpu().numpy(), ug))
-            B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
-        else:
-            K_ts, k_pop = ks_simulate_capital(k_opt, kg, Kg, zi, eps, k_pop)
-            B_new, r2g, r2b = alm_regress(K_ts, zi, T_discard)
-        R2 = (r2g, r2b)
-        diff_B = float(np.max(np.abs(B_new - B)))                              # :291
-        hist.append(B_new.copy())
-        if log:
-            log(f"ALM {it + 1}: B_new={B_new} diff={diff_B:.2e} R2={R2}")
-        if diff_B < tol_B:
-            break
-        B = update_B * B_new + (1 - update_B) * B                                # :300
-    out = dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, k_opt=k_opt, egm_iters=egm_iters, zi=zi)
-    if hist_sim:
-        out.update(slow_periods=slow, x_grid=x)
-    return out
+    run, zi, extra = _alm_simulation(simulate, prm, kg, Kg, T, population, uniforms, n_paths, nx)
+    k_opt, B0 = _alm_start(kg, K_size)                                         # :96-97
+    st = dict(k_opt=k_opt, egm_iters=[])
+
+    def solve(B):
+        R = ks_egm_solve(st["k_opt"], kg, Kg, B, P, prm, tol=tol_egm, max_iter=max_egm)
+        st["k_opt"] = R["k_opt"]
+        st["egm_iters"].append(R["iters"])
+        return R["k_opt"]
+    B, hist, R2, K_ts = _alm_loop(solve, run, lambda K: alm_regress_paths(K, zi, T_discard), B0,
+                                  max_iter_B, tol_B, update_B, log)
+    return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, **st, zi=zi, **extra)
 
 
 def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=100, tol_B=1e-6,
@@ -564,7 +527,6 @@ def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=
     krusell_smith_egm's keys plus `failed` (None when it ran through); every economy that does
     not fail equals its own krusell_smith_egm(simulate="histogram") run bit for bit."""
     import torch
-    from .ks import ks_egm_solve_batch_dev
     ecos = [_egm_economy(k_size, K_size, e) for e in economies]
     E = len(ecos)
     if E < 1:
@@ -626,14 +588,12 @@ def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=
                 continue
             B_new, r2g, r2b = alm_regress_paths(K_ts, zi, T_discard)
             res[e]["R2"] = (r2g, r2b)
-            diff_B = float(np.max(np.abs(B_new - B[e])))                       # :291
+            diff_B, done, B[e] = _alm_step(B[e], B_new, tol_B, update_B)       # :291-300
             res[e]["B_history"].append(B_new.copy())
             if log:
                 log(f"ALM {it + 1} economy {e}: B_new={B_new} diff={diff_B:.2e}")
-            if diff_B < tol_B:
-                continue
-            B[e] = update_B * B_new + (1 - update_B) * B[e]                      # :300
-            still.append(e)
+            if not done:
+                still.append(e)
         run = still
     ko_host = k_opt.cpu().numpy()
     for e in range(E):

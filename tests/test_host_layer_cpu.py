@@ -93,8 +93,8 @@ def test_tree_perm_is_a_permutation(perm_runs):
             assert -2 not in slots and slots.count(-1) == len(slots) - G
 
 
-def test_devbuf_edge_cases(tmp_path):
-    exe = _build(tmp_path, "devbuf_main.cpp",
+def _run_hip_host_program(tmp_path, src):
+    exe = _build(tmp_path, src,
                  ["-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include", f"-L{ROCM}/lib", "-lamdhip64",
                   f"-Wl,-rpath,{ROCM}/lib"])
     # no device visible; leak checking stays on for the program, off for the ROCm runtime's own
@@ -103,3 +103,12 @@ def test_devbuf_edge_cases(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     assert r.stdout.strip().endswith("done") and "FAILED" not in r.stdout
+
+
+def test_devbuf_edge_cases(tmp_path):
+    _run_hip_host_program(tmp_path, "devbuf_main.cpp")
+
+
+def test_host_ctx_named_buffers(tmp_path):
+    """The host tier's name -> buffer map (csrc/host_ctx.hpp) on malloc-backed memory."""
+    _run_hip_host_program(tmp_path, "host_ctx_main.cpp")
