@@ -176,6 +176,21 @@ __device__ __forceinline__ double group_fmax_d(double x) {
     x = fmax(x, dpp_d<0x4E>(x));
     return fmax(x, dpp_d<0x141>(x));
 }
+// Lanes per group of the tree kernel's fine-screen walk: each group of
+// kFineGroup consecutive lanes walks the 8-blocks that its own lanes passed in the confirmation,
+// the groups in lockstep, instead of every lane walking the wave's union.  64: the union walk
+// (what cooperating waves, R = 2, the lean bodies and labour keep).
+constexpr int kFineGroup = 8;
+
+// OR of a 64-bit mask over each group of eight consecutive lanes, left in every lane of the
+// group (the ladder of group_fmin_d on the two halves)
+__device__ __forceinline__ unsigned long long group_or_u64(unsigned long long m) {
+    static_assert(kFineGroup == 8 || kFineGroup == 64, "the ladder is written for eight lanes");
+    m |= dpp_u64<0xB1>(m);
+    m |= dpp_u64<0x4E>(m);
+    return m | dpp_u64<0x141>(m);
+}
+
 // the rest of the wave ladder from a value that already holds its group's min / max in every
 // lane: wave_fmin_d(x) == wave_rest_fmin_d(group_fmin_d(x)), the same operations
 __device__ __forceinline__ double wave_rest_fmin_d(double x) {

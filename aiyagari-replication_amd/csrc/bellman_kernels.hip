@@ -1064,6 +1064,13 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         // loose there.
         constexpr bool GRP = !LAB;
         constexpr int GL = kTreeGroup;
+        // The fine screens per lane group (GF): one-wave tiles with one
+        // state per lane keep, per group of kFineGroup lanes, the OR of the lanes' own
+        // confirmed blocks, and each group walks only its own blocks — the groups in lockstep,
+        // so a superblock takes as many trips as its busiest group has blocks, not as many as
+        // the wave's union.  Cooperating waves, the hybrid kernel, R = 2, the lean bodies and
+        // labour keep the union walk.
+        constexpr bool GF = GRP && W == 1 && R == 1 && !LEAN && !HY && kFineGroup < 64;
         double gB = __builtin_nan(""), gC = -__builtin_inf();
         auto set_G = [&]() __attribute__((always_inline)) {
             double bl = __builtin_nan(""), cl = -__builtin_inf();
@@ -1138,10 +1145,28 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         // instructions): the clamp stage is skipped, by a wave-uniform branch around it, when
         // all eight staged candidates lie below kfmin — all eight, not only those below k1:
         // the first wave vote looks at the unmasked eight.
-        auto fine = [&](int sbase, int k0, int k1, const double2 (&tk)[8])
-                        __attribute__((always_inline)) {
-            if (INS && (A.hitcount || A.trace)) nfine += k1 - k0;
-            const bool ncl = FAST && k0 + 8 <= kfmin;
+        // GF: k0 is the lane's own block (one per group), act whether its group still had one
+        // (a lane without reads a staged block and neither votes nor evaluates), and the
+        // clamp's branch is taken from ncl_sb, decided once per superblock from its highest
+        // passing block, so it stays wave-uniform.  The self-mask compares idx − k0 with the
+        // slot (k0 per lane: no add per slot), and the cut to the feasible range moves from the
+        // scalar vote to the lanes' bits, behind the first vote.  GF callers pass k1 = 0 (each
+        // lane's range end is kg − k0, taken where it is needed); the union callers leave act
+        // and ncl_sb at their defaults.  The per-superblock decision is coarser than the union
+        // walk's per-block one: every trip of a superblock whose highest passing block reaches
+        // kfmin keeps the clamp, its blocks below kfmin included.
+        // (instrumentation) nfine adds one lane's slot count per trip, the first active
+        // lane's: a trip that holds both a full block and the partial last block of the
+        // feasible range is counted by its lowest active group, 8 or the partial count.
+        auto fine = [&](int sbase, int k0, int k1, const double2 (&tk)[8], bool act = true,
+                        bool ncl_sb = false) __attribute__((always_inline)) {
+            if (INS && (A.hitcount || A.trace)) {
+                if constexpr (GF)  // (a trip counts once: the first active lane's block)
+                    nfine += readlane_i(min(8, kg - k0), __builtin_ctzll(__ballot(act)));
+                else nfine += k1 - k0;
+            }
+            const bool ncl = GF ? ncl_sb : (FAST && k0 + 8 <= kfmin);
+            const int dk = GF ? idx[0] - k0 : 0;
             if (INS && A.hitcount) npath[0] += ncl ? 0u : 1u, npath[1] += ncl ? 1u : 0u;
             bool pk[8];
 #pragma unroll
@@ -1175,8 +1200,12 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     for (int r = 0; r < R; ++r)
 #pragma unroll
                         for (int q = 0; q < LB; ++q) {
-                            const int lin = (l0 + q) + Nl * (k0 + g0 + gk);
-                            pass = pass || (t[(gk * R + r) * LB + q] >= kThr && lin != idx[r]);
+                            if constexpr (GF) {  // (Nl = 1, l0 = q = 0: lin = k0 + g0 + gk)
+                                pass = pass || (t[(gk * R + r) * LB + q] >= kThr && dk != g0 + gk);
+                            } else {
+                                const int lin = (l0 + q) + Nl * (k0 + g0 + gk);
+                                pass = pass || (t[(gk * R + r) * LB + q] >= kThr && lin != idx[r]);
+                            }
                         }
                     pk[g0 + gk] = pass;
                 }
@@ -1185,12 +1214,14 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                 bool pall = false;
 #pragma unroll
                 for (int kk = 0; kk < 8; ++kk) pall = pall || pk[kk];
-                if (!__any(pall)) return;
+                if (!__any(GF ? pall && act : pall)) return;
             }
             unsigned vote = 0;
+            const int nk = GF ? (act ? kg - k0 : 0) : 8;  // GF: this lane's slots inside the range
 #pragma unroll
-            for (int kk = 0; kk < 8; ++kk) vote |= (__any(pk[kk]) ? 1u : 0u) << kk;
-            vote &= (1u << (k1 - k0)) - 1u;
+            for (int kk = 0; kk < 8; ++kk)
+                vote |= (__any(GF ? pk[kk] && kk < nk : pk[kk]) ? 1u : 0u) << kk;
+            if constexpr (!GF) vote &= (1u << (k1 - k0)) - 1u;
             if (!vote) return;
             stamp(2);
             while (vote) {
@@ -1204,7 +1235,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     for (int q = 0; q < LB; ++q) {
                         const double c = coh[r][q] - tkk.x;
                         const int lin = (l0 + q) + Nl * k;
-                        if (lin != idx[r] && c > 0 &&
+                        if (lin != idx[r] && c > 0 && (!GF || kk < nk) &&
                             (tkk.y - B[r][q]) * aiy_ipow(c, NP) >= kThr) {
                             ++nhits;
                             const double val =
@@ -1272,8 +1303,11 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         // prep of superblock n+1 before finish of superblock n, so the candidate loads of n+1
         // are in flight while n is screened (a bar raised by n's exact path only makes n+1's
         // bound tests, done against the older bar, pass more: never fewer candidates).
+        // GF: gmo receives the lane's group mask — the OR over its kFineGroup lanes of their own
+        // confirmed blocks; the returned union is still what the staging and finish's LDS
+        // writes use
         auto prep = [&](int sb, int bsel, int bstep, double dm8, double a8, double2 (&st)[8],
-                        bool subsplit = false)
+                        unsigned long long& gmo, bool subsplit = false)
                         __attribute__((always_inline)) -> unsigned long long {
             stamp(0);
             const int sbase = sb << 9;  // first candidate of the superblock
@@ -1317,7 +1351,7 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                 // vote) — the wave's exact union, at one test per candidate block instead of
                 // one per block of every passing 64-block.
                 if (INS && (A.hitcount || A.trace)) nblk += __builtin_popcountll(pass);
-                unsigned long long keep = 0;
+                unsigned long long keep = 0, own = 0;
                 for (unsigned long long m = pass; m; m &= m - 1) {
                     const int u = __builtin_ctzll(m);
                     const double dv = readlane_d(dm8, u), av = readlane_d(a8, u);
@@ -1334,8 +1368,10 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
 #pragma unroll
                     for (int m2 = 0; m2 < RL; ++m2) p = p || t[m2] >= kThr;
                     if (__any(p)) keep |= 1ull << u;
+                    if constexpr (GF) own |= p ? 1ull << u : 0ull;
                 }
                 pass = keep;
+                if constexpr (GF) gmo = keep ? group_or_u64(own) : 0ull;
                 if (INS && A.trace && lane == 0) lane_pairs += __builtin_popcountll(pass);
                 stage(sbase, pass, st);
                 stamp(1);
@@ -1384,8 +1420,8 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             stamp(1);
             return pass;
         };
-        auto finish = [&](int sb, unsigned long long pass, const double2 (&st)[8])
-                          __attribute__((always_inline)) {
+        auto finish = [&](int sb, unsigned long long pass, const double2 (&st)[8],
+                          unsigned long long gm) __attribute__((always_inline)) {
             const int sbase = sb << 9;
             if constexpr (!LEAN)
 #pragma unroll
@@ -1403,6 +1439,39 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
                     const int b0 = __builtin_ctzll(pm);
                     load_tk(b0, tkA);
                     fine(sbase, sbase + (b0 << 3), min(sbase + (b0 << 3) + 8, kg), tkA);
+                }
+            }
+            if constexpr (GF) {
+                // Trips: every lane takes the lowest block left in its group's mask (ascending,
+                // as the union walk visited them); a group that has run out reads the wave's
+                // highest passing block, which is staged.  The walk ends when no group has a
+                // block left: as many trips as the busiest group has blocks.
+                pm = 0;
+                const int hb = 63 - __builtin_clzll(pass);
+                const bool ncl = FAST && sbase + (hb << 3) + 8 <= kfmin;
+                auto next = [&](int& k0) __attribute__((always_inline)) {
+                    const unsigned lo = (unsigned)gm, hi = (unsigned)(gm >> 32);
+                    const unsigned tl = lo ? (unsigned)__builtin_ctz(lo) : ~0u;
+                    const unsigned th = hi ? ((unsigned)__builtin_ctz(hi) | 32u) : ~0u;
+                    const int b = (int)min(min(tl, th), (unsigned)hb);
+                    gm &= gm - 1;
+                    k0 = sbase + (b << 3);
+                    return b;
+                };
+                int kA, kB;
+                bool actA = gm != 0, actB;
+                load_tk(next(kA), tkA);
+                for (;;) {
+                    actB = gm != 0;
+                    const bool moreB = __any(actB);
+                    if (moreB) load_tk(next(kB), tkB);
+                    fine(sbase, kA, 0, tkA, actA, ncl);
+                    if (!moreB) break;
+                    actA = gm != 0;
+                    const bool moreA = __any(actA);
+                    if (moreA) load_tk(next(kA), tkA);
+                    fine(sbase, kB, 0, tkB, actB, ncl);
+                    if (!moreA) break;
                 }
             }
             if (pm) load_tk(__builtin_ctzll(pm), tkA);
@@ -1438,9 +1507,10 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             if (INS) ++nsup;
             double d8, a8;
             load8(sfirst, d8, a8);
-            const unsigned long long p = prep(sfirst, wave, W, d8, a8, st_cur,
+            unsigned long long gm1 = 0;
+            const unsigned long long p = prep(sfirst, wave, W, d8, a8, st_cur, gm1,
                                               (A.variant & kVarDealBlocks) != 0);
-            if (p) finish(sfirst, p, st_cur);
+            if (p) finish(sfirst, p, st_cur, gm1);
             exchange();
             set_B();
         }
@@ -1517,26 +1587,27 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
         int cur = nsb > 0 ? next_sb() : -1;
         double pd = 0.0, pa = 0.0;
         if (cur >= 0) load8(cur, pd, pa);
-        unsigned long long pass_prev = 0;
+        unsigned long long pass_prev = 0, gm_cur = 0, gm_prev = 0;
         int sb_prev = -1;
         while (cur >= 0) {
             const double d8 = pd, a8 = pa;
             const int nxt = next_sb();
             if (nxt >= 0) load8(nxt, pd, pa);
-            const unsigned long long pc = prep(cur, 0, 1, d8, a8, st_cur);
+            const unsigned long long pc = prep(cur, 0, 1, d8, a8, st_cur, gm_cur);
             if constexpr (LEAN) {  // staged straight to LDS: screen it now
-                if (pc) finish(cur, pc, st_cur);
+                if (pc) finish(cur, pc, st_cur, gm_cur);
                 cur = nxt;
                 continue;
             }
-            if (pass_prev) finish(sb_prev, pass_prev, st_prev);
+            if (pass_prev) finish(sb_prev, pass_prev, st_prev, gm_prev);
 #pragma unroll
             for (int b = 0; b < 8; ++b) st_prev[b] = st_cur[b];
             pass_prev = pc;
+            gm_prev = gm_cur;
             sb_prev = cur;
             cur = nxt;
         }
-        if (pass_prev) finish(sb_prev, pass_prev, st_prev);
+        if (pass_prev) finish(sb_prev, pass_prev, st_prev, gm_prev);
     }
 
     exchange();
