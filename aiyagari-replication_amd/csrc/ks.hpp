@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include <vector>
 
@@ -81,6 +82,26 @@ struct KsOut {
 bool ks_fused_fits(int nk, int nK);
 int launch_ks_fused(const KsArgs& A, double* V, double* kopt, int* nfev, KsOut* out,
                     hipStream_t st);
+// The batched fused solve (ks_fused_vfi_batch_kernel): one workgroup per candidate economy.
+constexpr int64_t kVfiBatchMaxCand = 65535;  // one grid dimension
+struct KsVfiCand {   // what a candidate owns beside its slice table
+    double P[16];    // 4 x 4 row-major
+    double beta, k_min, k_max;
+};
+struct KsVfiBatchArgs {
+    int nk, nK, howard, max_vfi, C;
+    const double* k_grid;     // shared
+    const KsVfiCand* cand;    // [C]
+    const KsSlice* slice;     // [C][s * nK + K]
+    double tol;
+    double* value;            // [C][4][nK][nk] in/out
+    double* k_opt;            // [C][4][nK][nk] in/out
+    int64_t* iters;           // [C]
+    double* rel;              // [C]
+};
+// threads per economy: 1024, 512 or 256; 0: the library's choice for C (ks_vfi_batch_threads)
+int ks_vfi_batch_threads(int C);
+int launch_ks_fused_batch(const KsVfiBatchArgs& B, int threads, hipStream_t st);
 int launch_ks_slopes(const KsArgs& A, const double* V, double* dV, hipStream_t st);
 int launch_ks_grid_tables(const double* kg, int nk, double* tab, hipStream_t st);
 int launch_ks_slopes_cols(const KsArgs& A, const int* cols, int ncols, const double* V,

@@ -17,6 +17,7 @@
 //   fused    one workgroup holds the whole problem in LDS (reference size: 1,600 nodes) and runs
 //            the complete VFI loop — improvement every 5th iteration, H Howard sweeps, the
 //            relative-difference stop (:195-203) — in ONE launch (barriers between phases).
+//            The batch (ks_fused_vfi_batch_kernel) is the same body, one workgroup per economy.
 //   tiled    slopes / improve / howard / reldiff as separate grid-wide kernels (any size).
 #include <algorithm>
 
@@ -497,31 +498,68 @@ __global__ void ks_reldiff_kernel(KsArgs A, const double* __restrict__ V,
 // One workgroup, everything in LDS: kg | V | dV | Vn ; k_opt and v_old stay in registers.
 constexpr int kFusedThreads = 1024;
 constexpr int kFusedMaxPerThread = 4;  // nodes per thread
+constexpr int kFusedNodes = kFusedThreads * kFusedMaxPerThread;  // capacity of every geometry
 
-__global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, double* V_io,
-                                                                     double* kopt_io,
-                                                                     int* nfev_io, KsOut* out) {
+// Element r of a per-thread array that must stay in registers, r not a compile-time constant
+// (the rolled node loops of the geometries with many nodes per thread): the bits are moved
+// under a mask per element (a chain of selects is turned back into an indexed private array,
+// which lives in scratch).  Under a fully unrolled loop they fold to a[r] itself.
+template <int N>
+__device__ __forceinline__ double reg_get(const double (&a)[N], int r) {
+    unsigned long long u = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        u |= __builtin_bit_cast(unsigned long long, a[q]) & (q == r ? ~0ull : 0ull);
+    return __builtin_bit_cast(double, u);
+}
+template <int N>
+__device__ __forceinline__ void reg_set(double (&a)[N], int r, double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        const unsigned long long m = q == r ? ~0ull : 0ull;
+        a[q] = __builtin_bit_cast(double,
+                                  (__builtin_bit_cast(unsigned long long, a[q]) & ~m) | (b & m));
+    }
+}
+
+// The whole VFI loop of one economy in one workgroup of THREADS lanes, PER nodes per lane
+// (THREADS·PER >= 4,096 nodes): node n belongs to lane n mod THREADS.  The single solve
+// (ks_fused_vfi_kernel, <1024, 4>) and the batch (ks_fused_vfi_batch_kernel) both run this body;
+// it is the only copy of the loop.
+//
+// The geometry cannot change a result: a node's improvement and its Howard value are functions
+// of the LDS arrays of the previous phase (barriers between phases) and of that node alone, so
+// which lane evaluates the node is immaterial; and the stop statistic is a NaN-filtered fmax
+// over the nodes, which is associative and commutative (no rounding), so neither the lane that
+// holds a node nor the order of the reduction enters it.  The node loops are unrolled up to 4
+// nodes per lane (the single solve's code) and rolled beyond that.
+template <int THREADS, int PER>
+__device__ __forceinline__ void ks_fused_vfi_body(const KsArgs& A, double* V_io, double* kopt_io,
+                                                  int* nfev_io, int* it_out, double* rel_out) {
+    static_assert(THREADS * PER >= kFusedNodes && THREADS % 64 == 0, "capacity of ks_fused_fits");
+    constexpr int kUnroll = PER <= 4 ? PER : 1;
     extern __shared__ double lds[];
     const int nk = A.nk, n_all = A.nk * A.nK * 4;
     double* kg = lds;
     double* V = kg + nk;
     double* dV = V + n_all;
     double* Vn = dV + n_all;
-    __shared__ double s_red[kFusedThreads / 64];
+    __shared__ double s_red[THREADS / 64];
     __shared__ int s_flag;
     const int tid = threadIdx.x;
-    for (int q = tid; q < nk; q += blockDim.x) kg[q] = A.k_grid[q];
-    for (int q = tid; q < n_all; q += blockDim.x) V[q] = V_io[q];
-    double kopt[kFusedMaxPerThread], vold[kFusedMaxPerThread];
+    for (int q = tid; q < nk; q += THREADS) kg[q] = A.k_grid[q];
+    for (int q = tid; q < n_all; q += THREADS) V[q] = V_io[q];
+    double kopt[PER], vold[PER];
 #pragma unroll
-    for (int r = 0; r < kFusedMaxPerThread; ++r) {
-        int n = tid + r * kFusedThreads;
+    for (int r = 0; r < PER; ++r) {
+        int n = tid + r * THREADS;
         kopt[r] = n < n_all ? kopt_io[n] : 0.0;
         vold[r] = 0.0;
     }
     __syncthreads();
     auto slopes = [&]() {
-        for (int q = tid; q < n_all; q += blockDim.x)
+        for (int q = tid; q < n_all; q += THREADS)
             dV[q] = pchip_slope(kg, V + (q / nk) * nk, nk, q % nk);
         __syncthreads();
     };
@@ -529,19 +567,19 @@ __global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, d
     double rel = __builtin_nan("");
     for (it = 1; it <= A.max_vfi; ++it) {
 #pragma unroll
-        for (int r = 0; r < kFusedMaxPerThread; ++r) {
-            int n = tid + r * kFusedThreads;
+        for (int r = 0; r < PER; ++r) {
+            int n = tid + r * THREADS;
             if (n < n_all) vold[r] = V[n];  // value_old = value (:145)
         }
         KsView W{kg, V, dV};
         if ((it - 1) % 5 == 0) {  // policy improvement (:148-168)
             slopes();
-#pragma unroll
-            for (int r = 0; r < kFusedMaxPerThread; ++r) {
-                int n = tid + r * kFusedThreads;
+#pragma unroll kUnroll
+            for (int r = 0; r < PER; ++r) {
+                int n = tid + r * THREADS;
                 if (n < n_all) {
                     int nf = 0;
-                    kopt[r] = improve_node(A, W, n, &nf);
+                    reg_set(kopt, r, improve_node(A, W, n, &nf));
                     if (nfev_io) nfev_io[n] = nf;
                 }
             }
@@ -550,20 +588,20 @@ __global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, d
         for (int h = 0; h < A.howard; ++h) {  // Jacobi Howard sweeps (:172-192)
             slopes();
             KsView Wh{kg, V, dV};
-#pragma unroll
-            for (int r = 0; r < kFusedMaxPerThread; ++r) {
-                int n = tid + r * kFusedThreads;
-                if (n < n_all) Vn[n] = howard_node(A, Wh, n, kopt[r]);
+#pragma unroll kUnroll
+            for (int r = 0; r < PER; ++r) {
+                int n = tid + r * THREADS;
+                if (n < n_all) Vn[n] = howard_node(A, Wh, n, reg_get(kopt, r));
             }
             __syncthreads();
-            for (int q = tid; q < n_all; q += blockDim.x) V[q] = Vn[q];
+            for (int q = tid; q < n_all; q += THREADS) V[q] = Vn[q];
             __syncthreads();
         }
         // relative difference, NaN ignored (:195)
         double m = -1.0;
 #pragma unroll
-        for (int r = 0; r < kFusedMaxPerThread; ++r) {
-            int n = tid + r * kFusedThreads;
+        for (int r = 0; r < PER; ++r) {
+            int n = tid + r * THREADS;
             if (n < n_all) {
                 double d = fabs(V[n] - vold[r]) / (fabs(vold[r]) + 1e-10);
                 if (d == d) m = fmax(m, d);
@@ -574,7 +612,7 @@ __global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, d
         __syncthreads();
         if (tid == 0) {
             double mm = -1.0;
-            for (int q = 0; q < kFusedThreads / 64; ++q) mm = fmax(mm, s_red[q]);
+            for (int q = 0; q < THREADS / 64; ++q) mm = fmax(mm, s_red[q]);
             rel = mm < 0 ? __builtin_nan("") : mm;
             s_flag = (rel < A.tol) ? 1 : 0;
             s_red[0] = rel;
@@ -585,15 +623,58 @@ __global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, d
         __syncthreads();
     }
     if (it > A.max_vfi) it = A.max_vfi;
-    for (int q = tid; q < n_all; q += blockDim.x) V_io[q] = V[q];
+    for (int q = tid; q < n_all; q += THREADS) V_io[q] = V[q];
 #pragma unroll
-    for (int r = 0; r < kFusedMaxPerThread; ++r) {
-        int n = tid + r * kFusedThreads;
+    for (int r = 0; r < PER; ++r) {
+        int n = tid + r * THREADS;
         if (n < n_all) kopt_io[n] = kopt[r];
     }
-    if (tid == 0) {
+    *it_out = it;
+    *rel_out = rel;
+}
+
+__global__ __launch_bounds__(kFusedThreads) void ks_fused_vfi_kernel(KsArgs A, double* V_io,
+                                                                     double* kopt_io,
+                                                                     int* nfev_io, KsOut* out) {
+    int it;
+    double rel;
+    ks_fused_vfi_body<kFusedThreads, kFusedMaxPerThread>(A, V_io, kopt_io, nfev_io, &it, &rel);
+    if (threadIdx.x == 0) {
         out->iters = it;
         out->rel = rel;
+    }
+}
+
+// A6/A7 batch — C independent economies, workgroup c running ks_fused_vfi_body on candidate c's
+// value and k_opt blocks with its own slice table, P, beta, k_min and k_max (KsVfiCand, read
+// through workgroup-uniform addresses: scalar loads); k_grid, the sizes, howard, tol and max_vfi
+// are shared.  The candidates share nothing that is written: no workgroup waits for or signals
+// another.  The grid is exactly C workgroups of THREADS lanes; the three geometries give the
+// same results bit for bit (see ks_fused_vfi_body).
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void ks_fused_vfi_batch_kernel(KsVfiBatchArgs B) {
+    const int c = blockIdx.x;
+    const KsVfiCand& cd = B.cand[c];
+    KsArgs A{};
+    A.nk = B.nk;
+    A.nK = B.nK;
+    A.k_grid = B.k_grid;
+    A.P = cd.P;
+    A.slice = B.slice + (size_t)c * 4 * B.nK;
+    A.beta = cd.beta;
+    A.k_min = cd.k_min;
+    A.k_max = cd.k_max;
+    A.tol = B.tol;
+    A.howard = B.howard;
+    A.max_vfi = B.max_vfi;
+    const size_t n = (size_t)B.nk * B.nK * 4;
+    int it;
+    double rel;
+    ks_fused_vfi_body<THREADS, kFusedNodes / THREADS>(A, B.value + c * n, B.k_opt + c * n,
+                                                      nullptr, &it, &rel);
+    if (threadIdx.x == 0) {
+        B.iters[c] = it;
+        B.rel[c] = rel;
     }
 }
 
@@ -615,6 +696,45 @@ int launch_ks_fused(const KsArgs& A, double* V, double* kopt, int* nfev, KsOut* 
                                                                                   nfev, out);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
+}
+
+// Threads per economy of a batch of C.  What a CU can hold, by geometry:
+//   LDS (ks_fused_lds_bytes against 160 KiB per CU): the reference size k = 100, K = 4 takes
+//     39,200 B, so four workgroups fit; the largest size k = 256, K = 4 takes 100,352 B: one.
+//   registers (512 VGPRs per lane of a SIMD): 1,024 lanes are 4 waves per SIMD, hence 128 VGPRs
+//     (63 spilled, 128 B scratch); 512 lanes compile to 163 VGPRs, 256 lanes to 202, both
+//     without scratch — at 3 and 2 waves per SIMD, i.e. one 512-lane or two 256-lane workgroups
+//     per CU.  A full CU (16 waves) means 128 VGPRs however the waves are grouped.
+// Measured (profiles/ks_vfi_batch_ab.txt): a launch lasts as long as its slowest
+// economy and an economy is latency-bound, so 1,024 lanes are fastest at every C from 1 to
+// 1,024 (18.0 / 23.8 / 37.5 ms for one economy at 1,024 / 512 / 256 lanes; 88.7 / 116.4 /
+// 170.9 ms at C = 1,024); no narrower geometry passes the margin rule anywhere.
+int ks_vfi_batch_threads(int C) {
+    (void)C;
+    return 1024;
+}
+
+template <int THREADS>
+static int launch_vfi_batch_t(const KsVfiBatchArgs& B, size_t lds, hipStream_t st) {
+    if (lds > 64 * 1024)  // dynamic LDS past 64 KiB needs the attribute
+        AIY_TRY((raise_dynamic_lds<ks_fused_vfi_batch_kernel<THREADS>>(150 * 1024)));
+    ks_fused_vfi_batch_kernel<THREADS><<<B.C, THREADS, lds, st>>>(B);
+    AIY_HIP(hipGetLastError());
+    return AIY_OK;
+}
+
+int launch_ks_fused_batch(const KsVfiBatchArgs& B, int threads, hipStream_t st) {
+    if (B.C < 1 || B.C > kVfiBatchMaxCand || !ks_fused_fits(B.nk, B.nK))
+        return fail(AIY_BAD_SHAPE, "batched VFI solve: need 1 <= C <= 65,535 and a candidate "
+                                   "inside the one-workgroup rule (k_size x K_size x 4 <= 4,096)");
+    const size_t lds = ks_fused_lds_bytes(B.nk, B.nK);
+    if (threads == 0) threads = ks_vfi_batch_threads(B.C);
+    switch (threads) {
+        case 1024: return launch_vfi_batch_t<1024>(B, lds, st);
+        case 512: return launch_vfi_batch_t<512>(B, lds, st);
+        case 256: return launch_vfi_batch_t<256>(B, lds, st);
+    }
+    return fail(AIY_BAD_ARG, "batched VFI solve: threads per economy must be 1024, 512 or 256");
 }
 // column-shaped grid: block of 64·ceil(nk / 64) <= 256 lanes along k, columns along y
 static dim3 ks_col_block(int nk) { return dim3(std::min(256, (nk + 63) / 64 * 64)); }

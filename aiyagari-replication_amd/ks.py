@@ -165,3 +165,69 @@ def ks_egm_solve_batch_dev(k_opt, k_grid, K_grid, B, P, params, tol=1e-6, max_it
                                        ptr(iters), ptr(diff), ptr(status), ptr(scratch),
                                        stream_handle(stream)))
     return iters, diff, status, scratch
+
+
+def ks_vfi_solve_batch(value, k_opt, k_grid, K_grid, B, P, params, howard_steps=50, tol=1e-6,
+                       max_vfi=10000):
+    """A6/A7 at C candidate economies in one launch (ks_vfi_solve_batch): value and k_opt
+    (C, nk, nK, 4), K_grid (C, nK), B (C, 4), P (C, 4, 4), params (C, 13); a shared K_grid, B, P
+    or params (one candidate's shape) broadcasts.  Returns dict(value, k_opt (C, nk, nK, 4),
+    iters (C,), rel_diff (C,)); every candidate equals its own ks_vfi_solve bit for bit.  Sizes
+    past the one-workgroup rule (nk * nK * 4 <= 4,096) are refused: there is no tiled batch."""
+    V = np.asarray(value, np.float64)
+    ko = np.asarray(k_opt, np.float64)
+    if V.ndim != 4 or V.shape[3] != 4:
+        raise ValueError("value must be (C, k_size, K_size, 4)")
+    if ko.shape != V.shape:
+        raise ValueError("k_opt must have value's shape (C, k_size, K_size, 4)")
+    C_, nk, nK, _ = V.shape
+    kg = np.ascontiguousarray(k_grid, np.float64)
+    if kg.shape != (nk,):
+        raise ValueError("value must be (C, numel(k_grid), K_size, 4)")
+    Kg, Bc, Pc, prm = egm_batch_inputs(C_, nK, K_grid, B, P, params)
+    # candidate-major, each block k x K x 4 column-major = [4][nK][nk] row-major
+    Vd = np.ascontiguousarray(V.transpose(0, 3, 2, 1))
+    kd = np.ascontiguousarray(ko.transpose(0, 3, 2, 1))
+    iters = np.zeros(C_, np.int64)
+    rel = np.zeros(C_)
+    check(lib().ks_vfi_solve_batch(i64(C_), ptr(Vd), ptr(kd), ptr(kg), ptr(Kg), ptr(Bc), ptr(Pc),
+                                   ptr(prm), i64(nk), i64(nK), i64(howard_steps), d(tol),
+                                   i64(max_vfi), ptr(iters), ptr(rel)))
+    return dict(value=Vd.transpose(0, 3, 2, 1), k_opt=kd.transpose(0, 3, 2, 1), iters=iters,
+                rel_diff=rel)
+
+
+def ks_vfi_solve_batch_dev(value, k_opt, k_grid, K_grid, B, P, params, howard_steps=50, tol=1e-6,
+                           max_vfi=10000, out=None, scratch=None, stream=None):
+    """Device tier of ks_vfi_solve_batch: value and k_opt device tensors [C][4][nK][nk] (in/out),
+    k_grid a device tensor; K_grid, B, P, params host arrays as in ks_vfi_solve_batch.  `out` =
+    (iters int64, rel_diff float64) device tensors [C] and `scratch` a device byte tensor of
+    ks_vfi_batch_scratch_bytes(C, nK) are allocated when None.  value must hold no ±inf (NaN is
+    accepted) and k_grid must increase strictly: the caller's preconditions.  Asynchronous on
+    `stream` after the table upload; returns (iters, rel_diff, scratch)."""
+    import torch
+    from ._capi import stream_handle
+    C_, nS, nK, nk = value.shape
+    if nS != 4 or k_grid.numel() != nk:
+        raise ValueError("value must be [C][4][K_size][numel(k_grid)]")
+    if tuple(k_opt.shape) != tuple(value.shape):
+        raise ValueError("k_opt must have value's shape")
+    if not (value.is_contiguous() and k_opt.is_contiguous()):
+        raise ValueError("value and k_opt must be contiguous tensors")
+    Kg, Bc, Pc, prm = egm_batch_inputs(C_, nK, K_grid, B, P, params)
+    dev = value.device
+    lib().ks_vfi_batch_scratch_bytes.restype = C.c_int64
+    need = int(lib().ks_vfi_batch_scratch_bytes(i64(C_), i64(nK)))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    if scratch.numel() < need:
+        raise ValueError(f"scratch holds {scratch.numel()} bytes, the call needs {need}")
+    if out is None:
+        out = (torch.zeros(C_, dtype=torch.int64, device=dev),
+               torch.zeros(C_, dtype=torch.float64, device=dev))
+    iters, rel = out
+    check(lib().ks_vfi_solve_batch_dev(i64(C_), ptr(value), ptr(k_opt), ptr(k_grid), ptr(Kg),
+                                       ptr(Bc), ptr(Pc), ptr(prm), i64(nk), i64(nK),
+                                       i64(howard_steps), d(tol), i64(max_vfi), ptr(iters),
+                                       ptr(rel), ptr(scratch), stream_handle(stream)))
+    return iters, rel, scratch

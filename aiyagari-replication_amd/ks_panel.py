@@ -15,7 +15,8 @@ import numpy as np
 from . import calibration
 from ._capi import check, i64, lib, ptr, stream_handle
 from .ge import matlab_rand  # noqa: F401  (the fresh-session stream; exported from here too)
-from .ks import _per_candidate, ks_egm_solve, ks_egm_solve_batch_dev, ks_params, ks_vfi_solve
+from .ks import (_per_candidate, ks_egm_solve, ks_egm_solve_batch_dev, ks_params, ks_vfi_solve,
+                 ks_vfi_solve_batch_dev)
 
 
 def shock_draws(T: int, population: int) -> int:
@@ -448,17 +449,17 @@ def _alm_start(kg, K_size):
 def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B=100, tol_B=1e-6,
                       update_B=0.3, howard_steps=50, tol_vfi=1e-6, max_vfi=10000, T_discard=100,
                       uniforms=None, n_devices=1, log=None, simulate="panel", n_paths=1,
-                      nx=1000):
+                      nx=1000, **economy):
     """Krusell_Smith_VFI.m:4-296 end to end on the GPU kernels: shocks (F3), then per ALM
     iteration the VFI solve (A6/A7), the panel simulation (F2) and the host regression/update.
     Returns dict(B, B_history, R2, K_ts, value, k_opt, vfi_iters).
     simulate="histogram": the capital path comes from the histogram simulation (HistSim) on
     n_paths shock paths over an nx-point grid instead of the agent panel, and the regression is
     pooled over the paths (alm_regress_paths); K_ts and zi are then (T, n_paths).  `uniforms`
-    then holds n_paths * (T - 1) aggregate draws."""
+    then holds n_paths * (T - 1) aggregate draws.  `economy`: ks_params keywords plus K_min and
+    K_max (defaults: the script's), as krusell_smith_egm's."""
     _check_simulate(simulate)
-    prm = ks_params()
-    kg, Kg, P, V0 = calibration.krusell_smith(k_size=k_size, K_size=K_size)
+    prm, kg, Kg, P, V0 = _economy(k_size, K_size, economy)
     run, zi, extra = _alm_simulation(simulate, prm, kg, Kg, T, population, uniforms, n_paths, nx)
     k_opt, B0 = _alm_start(kg, K_size)
     st = dict(value=V0, k_opt=k_opt, vfi_iters=[])
@@ -474,15 +475,16 @@ def krusell_smith_vfi(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
     return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, **st, zi=zi, **extra)
 
 
-def _egm_economy(k_size, K_size, economy):
-    """(params, k_grid, K_grid, P) of one economy: ks_params keywords plus K_min and K_max."""
+def _economy(k_size, K_size, economy):
+    """(params, k_grid, K_grid, P, V0) of one economy: ks_params keywords plus K_min and K_max;
+    V0 is the VFI script's start (Krusell_Smith_VFI.m:98)."""
     eco = dict(economy)
     K_min, K_max = eco.pop("K_min", 30.0), eco.pop("K_max", 50.0)
     prm = ks_params(**eco)
-    kg, Kg, P, _ = calibration.krusell_smith(k_size=k_size, K_size=K_size, K_min=K_min,
-                                             K_max=K_max, beta=prm[0], k_min=prm[3],
-                                             k_max=prm[4], ug=prm[5], ub=prm[6])
-    return prm, kg, Kg, P
+    kg, Kg, P, V0 = calibration.krusell_smith(k_size=k_size, K_size=K_size, K_min=K_min,
+                                              K_max=K_max, beta=prm[0], k_min=prm[3],
+                                              k_max=prm[4], ug=prm[5], ub=prm[6])
+    return prm, kg, Kg, P, V0
 
 
 def krusell_smith_egm(k_size=100, K_size=4, T=1100, population=10000, max_iter_B=100, tol_B=1e-6,
@@ -497,7 +499,7 @@ def krusell_smith_egm(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
     in place of the panel, as krusell_smith_vfi's; K_ts and zi are then (T, n_paths) and
     `uniforms` holds n_paths * (T - 1) aggregate draws."""
     _check_simulate(simulate)
-    prm, kg, Kg, P = _egm_economy(k_size, K_size, economy)
+    prm, kg, Kg, P, _ = _economy(k_size, K_size, economy)
     run, zi, extra = _alm_simulation(simulate, prm, kg, Kg, T, population, uniforms, n_paths, nx)
     k_opt, B0 = _alm_start(kg, K_size)                                         # :96-97
     st = dict(k_opt=k_opt, egm_iters=[])
@@ -512,22 +514,27 @@ def krusell_smith_egm(k_size=100, K_size=4, T=1100, population=10000, max_iter_B
     return dict(B=B, B_history=hist, R2=R2, K_ts=K_ts, **st, zi=zi, **extra)
 
 
-def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=100, tol_B=1e-6,
-                            update_B=0.3, tol_egm=1e-6, max_egm=10000, T_discard=100,
-                            uniforms=None, n_paths=1, nx=1000, log=None):
-    """krusell_smith_egm(simulate="histogram") for several economies in lockstep.  `economies`:
-    a list of dicts of ks_params keywords plus K_min / K_max; all share k_min and k_max (hence
-    k_grid and x_grid), the sizes and the n_paths shock paths, each has its own params, P, K_grid
-    and B.  One ALM round is one ks_egm_solve_batch_dev over the economies still running (the
-    policies stay on the device), one histogram launch of (running economies) x n_paths
-    workgroups with one policy per path, K_ts back to the host and one pooled regression per
-    economy.  An economy leaves when its diff_B < tol_B, or when it fails: an EGM status != 0
-    (`failed` = "egm"; it is not simulated) or a non-positive or non-finite K_ts in the
-    regression window (`failed` = "K_ts").  Returns one dict per economy with
-    krusell_smith_egm's keys plus `failed` (None when it ran through); every economy that does
-    not fail equals its own krusell_smith_egm(simulate="histogram") run bit for bit."""
+def _policy_rows(x):
+    """k x K x 4 (MATLAB) as the device tiers' [4][nK][nk]."""
+    return np.ascontiguousarray(np.asarray(x, np.float64).transpose(2, 1, 0))
+
+
+def _alm_lockstep(economies, make_solver, iters_key, fail_name, k_size, K_size, T, max_iter_B,
+                  tol_B, update_B, T_discard, uniforms, n_paths, nx, log):
+    """The histogram ALM loop of several economies in lockstep, shared by
+    krusell_smith_egm_batch and krusell_smith_vfi_batch.  The economies share k_min and k_max
+    (hence k_grid and x_grid), the sizes and the n_paths shock paths; each has its own params, P,
+    K_grid and B.  `make_solver(ecos, kg_dev, dev)` returns (solve, finish): solve(idx, Kg, B,
+    P, prm) runs one batched solve of the economies idx (a device index tensor) on the solver's
+    own device-resident state and returns (k_opt [R][4][nK][nk] on the device, iters (R,),
+    status (R,)); finish(res) stores that state into the result dicts.  One round: one solve,
+    one histogram launch of (economies with status 0) x n_paths workgroups with one policy per
+    path, K_ts back to the host and one pooled regression per economy.  An economy leaves when
+    its diff_B < tol_B, or when it fails: status != 0 (`failed` = fail_name; it is not
+    simulated) or a non-positive or non-finite K_ts in the regression window (`failed` =
+    "K_ts")."""
     import torch
-    ecos = [_egm_economy(k_size, K_size, e) for e in economies]
+    ecos = [_economy(k_size, K_size, e) for e in economies]
     E = len(ecos)
     if E < 1:
         raise ValueError("need at least one economy")
@@ -544,30 +551,23 @@ def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=
     # path e * n_paths + p of the launch is shock path p: a prefix serves any number of economies
     sim = HistSimMulti(kg, x, np.tile(zi, (1, E)), np.zeros((2, nx)))
     dev = sim.lam.device
-    kg_dev = sim.k_grid
-    k0 = 0.9 * np.repeat(np.repeat(kg[None, None, :], K_size, 1), 4, 0)       # [4][nK][nk], :96
-    k_opt = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(k0, (E,) + k0.shape)),
-                            device=dev)
+    solve, finish = make_solver(ecos, sim.k_grid, dev)
     lam = np.stack([np.broadcast_to(hist_start(x, Kg[e, 0], ug[e]), (n_paths, 2, nx))
                     for e in range(E)])
     B = np.tile(np.array([0.0, 1.0, 0.0, 1.0]), (E, 1))                        # :97
-    res = [dict(B=B[e].copy(), B_history=[], R2=(0.0, 0.0), K_ts=None, k_opt=None, egm_iters=[],
-                zi=zi, slow_periods=None, x_grid=x, failed=None) for e in range(E)]
+    res = [dict(B=B[e].copy(), B_history=[], R2=(0.0, 0.0), K_ts=None, k_opt=None, zi=zi,
+                slow_periods=None, x_grid=x, failed=None, **{iters_key: []}) for e in range(E)]
     run = list(range(E))
     for it in range(max_iter_B):
         if not run:
             break
         idx = torch.as_tensor(run, device=dev)
-        ko = k_opt[idx]
-        iters, _, status, _ = ks_egm_solve_batch_dev(ko, kg_dev, Kg[run], B[run], P[run],
-                                                     prm[run], tol=tol_egm, max_iter=max_egm)
-        iters, status = iters.cpu().numpy(), status.cpu().numpy()
-        k_opt[idx] = ko
+        ko, iters, status = solve(idx, Kg[run], B[run], P[run], prm[run])
         good = [r for r in range(len(run)) if status[r] == 0]
         for r, e in enumerate(run):
-            res[e]["egm_iters"].append(int(iters[r]))
+            res[e][iters_key].append(int(iters[r]))
             if status[r] != 0:
-                res[e]["failed"] = "egm"
+                res[e]["failed"] = fail_name
         K_all = slow = lam_new = None
         if good:
             sim.set_lam(np.concatenate([lam[run[r]] for r in good]))
@@ -595,11 +595,86 @@ def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=
             if not done:
                 still.append(e)
         run = still
-    ko_host = k_opt.cpu().numpy()
     for e in range(E):
         res[e]["B"] = B[e].copy()
-        res[e]["k_opt"] = np.asfortranarray(ko_host[e].transpose(2, 1, 0))
+    finish(res)
     return res
+
+
+def _store_policies(res, key, dev_blocks):
+    """The device blocks [E][4][nK][nk] into res[e][key] as k x K x 4 column-major arrays."""
+    host = dev_blocks.cpu().numpy()
+    for e, r in enumerate(res):
+        r[key] = np.asfortranarray(host[e].transpose(2, 1, 0))
+
+
+def krusell_smith_egm_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=100, tol_B=1e-6,
+                            update_B=0.3, tol_egm=1e-6, max_egm=10000, T_discard=100,
+                            uniforms=None, n_paths=1, nx=1000, log=None):
+    """krusell_smith_egm(simulate="histogram") for several economies in lockstep.  `economies`:
+    a list of dicts of ks_params keywords plus K_min / K_max; all share k_min and k_max (hence
+    k_grid and x_grid), the sizes and the n_paths shock paths, each has its own params, P, K_grid
+    and B.  One ALM round is one ks_egm_solve_batch_dev over the economies still running (the
+    policies stay on the device), one histogram launch of (running economies) x n_paths
+    workgroups with one policy per path, K_ts back to the host and one pooled regression per
+    economy.  An economy leaves when its diff_B < tol_B, or when it fails: an EGM status != 0
+    (`failed` = "egm"; it is not simulated) or a non-positive or non-finite K_ts in the
+    regression window (`failed` = "K_ts").  Returns one dict per economy with
+    krusell_smith_egm's keys plus `failed` (None when it ran through); every economy that does
+    not fail equals its own krusell_smith_egm(simulate="histogram") run bit for bit."""
+    import torch
+
+    def make_solver(ecos, kg_dev, dev):
+        k0 = _policy_rows(_alm_start(ecos[0][1], K_size)[0])                   # :96
+        k_opt = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(k0, (len(ecos),) + k0.shape)),
+                                device=dev)
+
+        def solve(idx, Kg, B, P, prm):
+            ko = k_opt[idx]
+            iters, _, status, _ = ks_egm_solve_batch_dev(ko, kg_dev, Kg, B, P, prm, tol=tol_egm,
+                                                         max_iter=max_egm)
+            k_opt[idx] = ko
+            return ko, iters.cpu().numpy(), status.cpu().numpy()
+        return solve, lambda res: _store_policies(res, "k_opt", k_opt)
+    return _alm_lockstep(economies, make_solver, "egm_iters", "egm", k_size, K_size, T,
+                         max_iter_B, tol_B, update_B, T_discard, uniforms, n_paths, nx, log)
+
+
+def krusell_smith_vfi_batch(economies, k_size=100, K_size=4, T=1100, max_iter_B=100, tol_B=1e-6,
+                            update_B=0.3, howard_steps=50, tol_vfi=1e-6, max_vfi=10000,
+                            T_discard=100, uniforms=None, n_paths=1, nx=1000, log=None):
+    """krusell_smith_vfi(simulate="histogram") for several economies in lockstep, the VFI twin
+    of krusell_smith_egm_batch (same `economies`, same sharing rules).  One ALM round is one
+    ks_vfi_solve_batch_dev over the economies still running (one workgroup each; value and
+    policy stay on the device and are warm from the economy's previous round), one histogram
+    launch with one policy per path and one pooled regression per economy.  An economy leaves
+    when its diff_B < tol_B, or with `failed` = "K_ts" on a non-positive or non-finite K_ts in
+    the regression window.  k_size x K_size x 4 must fit the one-workgroup rule (<= 4,096
+    nodes).  Returns one dict per economy with krusell_smith_vfi's keys plus `failed`; every
+    economy equals its own krusell_smith_vfi(simulate="histogram", **economy) run bit for bit."""
+    import torch
+
+    def make_solver(ecos, kg_dev, dev):
+        k0 = _policy_rows(_alm_start(ecos[0][1], K_size)[0])                   # :97
+        k_opt = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(k0, (len(ecos),) + k0.shape)),
+                                device=dev)
+        value = torch.as_tensor(np.stack([_policy_rows(e[4]) for e in ecos]), device=dev)  # :98
+
+        def solve(idx, Kg, B, P, prm):
+            V, ko = value[idx], k_opt[idx]
+            iters, _, _ = ks_vfi_solve_batch_dev(V, ko, kg_dev, Kg, B, P, prm,
+                                                 howard_steps=howard_steps, tol=tol_vfi,
+                                                 max_vfi=max_vfi)
+            value[idx] = V
+            k_opt[idx] = ko
+            return ko, iters.cpu().numpy(), np.zeros(len(Kg), np.int32)
+
+        def finish(res):
+            _store_policies(res, "k_opt", k_opt)
+            _store_policies(res, "value", value)
+        return solve, finish
+    return _alm_lockstep(economies, make_solver, "vfi_iters", None, k_size, K_size, T, max_iter_B,
+                         tol_B, update_B, T_discard, uniforms, n_paths, nx, log)
 
 
 def hist_carry(lam, ug):

@@ -246,6 +246,25 @@ int ks_vfi_solve_sharded(double* value, double* k_opt, const double* k_grid,
                          double tol, int64_t max_vfi, int n_shards, int depth, int64_t* iters,
                          double* rel_diff);
 
+/* A6+A7 at C candidate economies in one launch: workgroup c runs ks_vfi_solve's one-workgroup
+ * loop (improvement on iterations 1, 6, 11, ..., `howard_steps` Jacobi sweeps with the slopes
+ * rebuilt before each, the NaN-ignoring relative-difference stop) on candidate c's own value and
+ * k_opt with its own K_grid row, B, P and params; k_grid, the sizes, howard_steps, tol and
+ * max_vfi are shared.  Layouts as ks_vfi_solve, candidate-major: value and k_opt [C] of
+ * k x K x 4 column-major (in/out), K_grid [C][nK], B [C][4], P [C] of MATLAB 4 x 4, params
+ * [C][13]; iters, rel_diff [C].  Candidate c's value, k_opt, iters and rel_diff equal one
+ * ks_vfi_solve call's bit for bit; a candidate cannot affect another (a NaN value block runs to
+ * max_vfi on its own).  Refused before any device work: NULL arguments, C outside [1, 65,535],
+ * k_size < 3, max_vfi outside [1, 2^31), a k_grid that is not strictly increasing, ±inf in a
+ * candidate's value (AIY_NON_FINITE naming the candidate; NaN is accepted), and a size past the
+ * one-workgroup rule (k_size * K_size * 4 <= 4,096 nodes) -> AIY_BAD_SHAPE: the batch has NO
+ * tiled fallback (ks_vfi_solve runs such sizes tiled, one economy per call).  Scratch: the
+ * library's cached host-tier buffers. */
+int ks_vfi_solve_batch(int64_t C, double* value, double* k_opt, const double* k_grid,
+                       const double* K_grid, const double* B, const double* P,
+                       const double* params, int64_t nk, int64_t nK, int64_t howard_steps,
+                       double tol, int64_t max_vfi, int64_t* iters, double* rel_diff);
+
 /* A8: the EGM policy iteration of Krusell_Smith_EGM.m:129-209 for the current B (replaces the
  * `for egm_iter = 1:max_egm` loop, :130-209).  k_opt: k_size x K_size x 4, in/out (:96 start).
  * Gauss-Seidel over (s_i outer, K_i inner) exactly as the script: each (s, K) column is
@@ -756,6 +775,24 @@ int ks_egm_solve_batch_dev(int64_t C, double* k_opt, const double* k_grid, const
                            const double* B, const double* P, const double* params, int64_t nk,
                            int64_t nK, double tol, int64_t max_iter, int64_t* iters, double* diff,
                            int32_t* status, void* scratch, void* stream);
+
+/* ---- A6/A7 batch device tier (ks_vfi_solve_batch): value and k_opt [C][4][K_size][k_size]
+ * (in/out; k_opt in the layout ks_simulate_hist_multi_dev reads, so the two launches of an ALM
+ * round need no repacking), k_grid, iters (int64) and rel_diff [C] in HBM; K_grid [C][K_size],
+ * B [C][4], P [C] of MATLAB 4 x 4 and params [C][13] are HOST arrays (the slice tables are libm
+ * on the host, as in ks_vfi_solve).  Host arguments and shapes are validated before any device
+ * work; preconditions on device contents are the caller's: k_grid strictly increasing, value
+ * finite or NaN (no ±inf).  No tiled fallback: a size past the one-workgroup rule is
+ * AIY_BAD_SHAPE.  Scratch is ks_vfi_batch_scratch_bytes(C, K_size) bytes of device memory owned
+ * by the caller and receives the host-built candidate tables.  The call waits for that upload
+ * (one synchronisation of `stream`), then enqueues the one launch and returns; the outputs are
+ * valid once `stream` has run it. */
+int64_t ks_vfi_batch_scratch_bytes(int64_t C, int64_t nK);
+int ks_vfi_solve_batch_dev(int64_t C, double* value, double* k_opt, const double* k_grid,
+                           const double* K_grid, const double* B, const double* P,
+                           const double* params, int64_t nk, int64_t nK, int64_t howard_steps,
+                           double tol, int64_t max_vfi, int64_t* iters, double* rel_diff,
+                           void* scratch, void* stream);
 
 #ifdef __cplusplus
 }
