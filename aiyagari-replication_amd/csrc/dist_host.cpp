@@ -264,6 +264,42 @@ int dist_stationary_batch_dev(aiy_ws* ws, int64_t C, const double* lam0, const i
     return AIY_OK;
 }
 
+// The host entries' staging and read-back, for C policies (aiy_dist_stationary: C = 1); each entry
+// runs its own device tier in between.  Layouts: vfi_layout → N x Na column-major; else Na x N
+// column-major (== [N][Na]).
+struct DistStaged {
+    double *a, *P, *l0, *l1, *kp = nullptr, *K;
+    int* idx = nullptr;
+};
+
+static int dist_stage(HostCtx* c, int64_t C, const int32_t* policy_idx, const double* policy_k,
+                      int vfi_layout, const double* a_grid, const double* P, int64_t N, int64_t Na,
+                      const double* lambda, DistStaged* D) {
+    const size_t n = (size_t)N * Na * C;
+    std::vector<double> s1(N, 1.0);  // (only a and P are used here)
+    double* ds;
+    AIY_TRY(stage_common(c, a_grid, s1.data(), P, N, Na, &D->a, &ds, &D->P));
+    auto rows_up = [&](const char* name, const double* src, double** dev) {
+        return vfi_layout ? c->up_rows(name, src, N, Na, C, dev) : c->up(name, src, n, dev);
+    };
+    if (policy_idx)
+        AIY_TRY(c->up_own("dist_idx", idx_rows0(policy_idx, vfi_layout, N, Na, C), &D->idx));
+    else
+        AIY_TRY(rows_up("dist_kp", policy_k, &D->kp));
+    AIY_TRY(rows_up("dist_l0", lambda, &D->l0));
+    AIY_TRY(c->room("dist_l1", n, &D->l1));
+    return c->room("dist_K", std::max<size_t>((size_t)C, 2), &D->K);
+}
+
+// λ and K of the C candidates back (synchronises)
+static int dist_back(HostCtx* c, const DistStaged& D, int64_t C, int vfi_layout, int64_t N,
+                     int64_t Na, double* lambda, double* k_supply) {
+    AIY_TRY(c->down(k_supply, D.K, (size_t)C));
+    if (vfi_layout) return c->down_rows(lambda, D.l1, N, Na, C);
+    AIY_TRY(c->down(lambda, D.l1, (size_t)N * Na * C));
+    return c->sync();
+}
+
 }  // namespace aiy
 
 using namespace aiy;
@@ -298,45 +334,13 @@ int aiy_dist_stationary(const int32_t* policy_idx, const double* policy_k, int v
     std::lock_guard<std::mutex> lk(host_mutex());
     HostCtx* c;
     AIY_TRY(get_ctx(N, Na, 1, &c));
-    std::vector<double> s1(N, 1.0);
-    double *da, *ds, *dP, *dl0, *dl1, *dkp = nullptr, *dK;
-    int* didx = nullptr;
-    AIY_TRY(stage_common(c, a_grid, s1.data(), P, N, Na, &da, &ds, &dP));
-    size_t n = (size_t)N * Na, nb = n * sizeof(double);
-    AIY_TRY(c->buf("dist_l0", nb, (void**)&dl0));
-    AIY_TRY(c->buf("dist_l1", nb, (void**)&dl1));
-    AIY_TRY(c->buf("dist_K", 16, (void**)&dK));
-    // layouts: vfi_layout → N x Na column-major; else Na x N column-major (== [N][Na])
-    std::vector<double> rows(n);
-    auto to_rows = [&](const double* src) {
-        if (vfi_layout) cm_to_rows(src, N, Na, rows.data());
-        else memcpy(rows.data(), src, nb);
-    };
-    if (policy_idx) {
-        std::vector<int> ib(n);
-        for (int64_t i = 0; i < N; ++i)
-            for (int64_t j = 0; j < Na; ++j)
-                ib[i * Na + j] = (vfi_layout ? policy_idx[i + j * N] : policy_idx[j + i * Na]) - 1;
-        AIY_TRY(c->buf("dist_idx", n * sizeof(int), (void**)&didx));
-        AIY_HIP(hipMemcpyAsync(didx, ib.data(), n * sizeof(int), hipMemcpyHostToDevice, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-    } else {
-        AIY_TRY(c->buf("dist_kp", nb, (void**)&dkp));
-        to_rows(policy_k);
-        AIY_HIP(hipMemcpyAsync(dkp, rows.data(), nb, hipMemcpyHostToDevice, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-    }
-    to_rows(lambda);
-    AIY_HIP(hipMemcpyAsync(dl0, rows.data(), nb, hipMemcpyHostToDevice, c->st));
+    DistStaged D;
+    AIY_TRY(dist_stage(c, 1, policy_idx, policy_k, vfi_layout, a_grid, P, N, Na, lambda, &D));
     double d = NAN;
     int64_t it = 0;
-    AIY_TRY(dist_stationary_dev(c->ws, dl0, didx, dkp, da, dP, tol, max_iter, dl1, dK, &it, &d,
-                                c->st));
-    AIY_HIP(hipMemcpyAsync(rows.data(), dl1, nb, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(k_supply, dK, sizeof(double), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
-    if (vfi_layout) rows_to_cm(rows.data(), N, Na, lambda);
-    else memcpy(lambda, rows.data(), nb);
+    AIY_TRY(dist_stationary_dev(c->ws, D.l0, D.idx, D.kp, D.a, D.P, tol, max_iter, D.l1, D.K, &it,
+                                &d, c->st));
+    AIY_TRY(dist_back(c, D, 1, vfi_layout, N, Na, lambda, k_supply));
     *iters = it;
     *dist = d;
     return AIY_OK;
@@ -378,50 +382,11 @@ int aiy_dist_stationary_batch(int64_t C, const int32_t* policy_idx, const double
     std::lock_guard<std::mutex> lk(host_mutex());
     HostCtx* c;
     AIY_TRY(get_ctx(N, Na, 1, &c));
-    std::vector<double> s1(N, 1.0);
-    double *da, *ds, *dP, *dl0, *dl1, *dkp = nullptr, *dK;
-    int* didx = nullptr;
-    AIY_TRY(stage_common(c, a_grid, s1.data(), P, N, Na, &da, &ds, &dP));
-    const size_t n = (size_t)N * Na, nb = n * sizeof(double);
-    AIY_TRY(c->buf("distb_l0", nb * C, (void**)&dl0));
-    AIY_TRY(c->buf("distb_l1", nb * C, (void**)&dl1));
-    AIY_TRY(c->buf("distb_K", sizeof(double) * C, (void**)&dK));
-    // layouts: vfi_layout → N x Na column-major; else Na x N column-major (== [N][Na])
-    std::vector<double> rows(n * C);
-    auto to_rows = [&](const double* src) {
-        for (int64_t q = 0; q < C; ++q) {
-            if (vfi_layout) cm_to_rows(src + q * n, N, Na, rows.data() + q * n);
-            else memcpy(rows.data() + q * n, src + q * n, nb);
-        }
-    };
-    if (policy_idx) {
-        std::vector<int> ib(n * C);
-        for (int64_t q = 0; q < C; ++q)
-            for (int64_t i = 0; i < N; ++i)
-                for (int64_t j = 0; j < Na; ++j)
-                    ib[q * n + i * Na + j] =
-                        (vfi_layout ? policy_idx[q * n + i + j * N] : policy_idx[q * n + j + i * Na]) - 1;
-        AIY_TRY(c->buf("distb_idx", n * C * sizeof(int), (void**)&didx));
-        AIY_HIP(hipMemcpyAsync(didx, ib.data(), n * C * sizeof(int), hipMemcpyHostToDevice, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-    } else {
-        AIY_TRY(c->buf("distb_kp", nb * C, (void**)&dkp));
-        to_rows(policy_k);
-        AIY_HIP(hipMemcpyAsync(dkp, rows.data(), nb * C, hipMemcpyHostToDevice, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-    }
-    to_rows(lambda);
-    AIY_HIP(hipMemcpyAsync(dl0, rows.data(), nb * C, hipMemcpyHostToDevice, c->st));
-    AIY_TRY(dist_stationary_batch_dev(c->ws, C, dl0, didx, dkp, da, dP, tol, max_iter, dl1, dK,
-                                      iters, dist, c->st));
-    AIY_HIP(hipMemcpyAsync(rows.data(), dl1, nb * C, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(k_supply, dK, sizeof(double) * C, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
-    for (int64_t q = 0; q < C; ++q) {
-        if (vfi_layout) rows_to_cm(rows.data() + q * n, N, Na, lambda + q * n);
-        else memcpy(lambda + q * n, rows.data() + q * n, nb);
-    }
-    return AIY_OK;
+    DistStaged D;
+    AIY_TRY(dist_stage(c, C, policy_idx, policy_k, vfi_layout, a_grid, P, N, Na, lambda, &D));
+    AIY_TRY(dist_stationary_batch_dev(c->ws, C, D.l0, D.idx, D.kp, D.a, D.P, tol, max_iter, D.l1,
+                                      D.K, iters, dist, c->st));
+    return dist_back(c, D, C, vfi_layout, N, Na, lambda, k_supply);
 }
 
 }  // extern "C"

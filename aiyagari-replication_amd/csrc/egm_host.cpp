@@ -245,12 +245,11 @@ static int egm_host(double* pc, const double* a, const double* s, const double* 
     AIY_TRY(get_ctx(N, Na, 1, &c));
     double *da, *ds, *dP, *dc0, *dc1, *dpk, *dpl;
     AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
-    size_t nb = sizeof(double) * N * Na;
-    AIY_TRY(c->buf("egm_c0", nb, (void**)&dc0));
-    AIY_TRY(c->buf("egm_c1", nb, (void**)&dc1));
-    AIY_TRY(c->buf("pk", nb, (void**)&dpk));
-    AIY_TRY(c->buf("pl", nb, (void**)&dpl));
-    AIY_HIP(hipMemcpyAsync(dc0, pc, nb, hipMemcpyHostToDevice, c->st));
+    const size_t n = (size_t)N * Na;
+    AIY_TRY(c->up("egm_c0", pc, n, &dc0));
+    AIY_TRY(c->room("egm_c1", n, &dc1));
+    AIY_TRY(c->room("pk", n, &dpk));
+    AIY_TRY(c->room("pl", n, &dpl));
     double d = 1.0;
     int64_t it = 0;
     double* cur = dc0;
@@ -276,10 +275,10 @@ static int egm_host(double* pc, const double* a, const double* s, const double* 
         }
     }
     double* dst = solve ? pc : pcn_out;
-    if (dst) AIY_HIP(hipMemcpyAsync(dst, cur, nb, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(pk_out, dpk, nb, hipMemcpyDeviceToHost, c->st));
-    if (labor && pl_out) AIY_HIP(hipMemcpyAsync(pl_out, dpl, nb, hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
+    if (dst) AIY_TRY(c->down(dst, cur, n));
+    AIY_TRY(c->down(pk_out, dpk, n));
+    if (labor && pl_out) AIY_TRY(c->down(pl_out, dpl, n));
+    AIY_TRY(c->sync());
     *dist = d;
     if (iters) *iters = it;
     return AIY_OK;

@@ -26,11 +26,6 @@ HostCtx::~HostCtx() {
     if (st) (void)hipStreamDestroy(st);
 }
 
-int copy_status(hipError_t e, const char* what) {
-    if (e == hipSuccess) return AIY_OK;
-    return fail(AIY_HIP_ERROR, "hipMemcpyAsync (%s) failed: %s", what, hipGetErrorString(e));
-}
-
 int get_ctx(int64_t N, int64_t Na, int64_t Nl, HostCtx** out) {
     int dev = 0;
     int ndev = 0;
@@ -52,16 +47,6 @@ int get_ctx(int64_t N, int64_t Na, int64_t Nl, HostCtx** out) {
 }
 
 std::mutex& host_mutex() { return g_mu; }
-
-// MATLAB N x Na column-major -> [N][Na] row-major
-void cm_to_rows(const double* cm, int64_t N, int64_t Na, double* rows) {
-    for (int64_t j = 0; j < Na; ++j)
-        for (int64_t i = 0; i < N; ++i) rows[i * Na + j] = cm[i + j * N];
-}
-void rows_to_cm(const double* rows, int64_t N, int64_t Na, double* cm) {
-    for (int64_t j = 0; j < Na; ++j)
-        for (int64_t i = 0; i < N; ++i) cm[i + j * N] = rows[i * Na + j];
-}
 
 int check_grid(const double* a, int64_t Na) {
     if (!a) return fail(AIY_BAD_ARG, "a_grid is NULL");
@@ -89,125 +74,70 @@ int check_grid_strict(const double* a, int64_t Na) {
 // stage the common Aiyagari inputs (a_grid, s, P) on the device; P transposed to row-major
 int stage_common(HostCtx* c, const double* a, const double* s, const double* P, int64_t N,
                  int64_t Na, double** da, double** ds, double** dP) {
-    AIY_TRY(c->buf("a", sizeof(double) * Na, (void**)da));
-    AIY_TRY(c->buf("s", sizeof(double) * N, (void**)ds));
-    AIY_TRY(c->buf("P", sizeof(double) * N * N, (void**)dP));
-    std::vector<double> Pr(N * N);
-    for (int64_t i = 0; i < N; ++i)
-        for (int64_t m = 0; m < N; ++m) Pr[i * N + m] = P[i + m * N];
-    AIY_HIP(hipMemcpyAsync(*da, a, sizeof(double) * Na, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(*ds, s, sizeof(double) * N, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(*dP, Pr.data(), sizeof(double) * N * N, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipStreamSynchronize(c->st));
+    AIY_TRY(c->up("a", a, (size_t)Na, da));
+    AIY_TRY(c->up("s", s, (size_t)N, ds));
+    AIY_TRY(c->up_rows("P", P, N, N, 1, dP));
+    AIY_TRY(c->sync());
     aiy_ws_invalidate(c->ws);  // the staged a/s contents may differ from the last call
     return AIY_OK;
 }
 
-static int vfi_host(const double* v_old_cm, const double* a, const double* s, const double* P,
-                    int64_t N, int64_t Na, double r, double w, double beta, double sigma,
-                    bool solve, double tol, int64_t max_iter, double* v_old_out_cm,
-                    double* v_new_cm, double* pk_cm, double* pc_cm, int32_t* idx_cm,
-                    int64_t* iters) {
-    if (!v_old_cm || !s || !P || !v_new_cm || !pk_cm || !pc_cm)
+std::vector<int> idx_rows0(const int32_t* idx1, int vfi_layout, int64_t N, int64_t Na, int64_t C) {
+    const size_t n = (size_t)N * Na;
+    std::vector<int> out(n * (size_t)C, 0);
+    if (!idx1) return out;
+    if (vfi_layout)
+        for (int64_t q = 0; q < C; ++q) cm_to_rows(idx1 + q * n, N, Na, out.data() + q * n);
+    else
+        out.assign(idx1, idx1 + out.size());
+    for (int& k : out) k -= 1;
+    return out;
+}
+
+// The host body of the four VFI entries, arrays N x Na column-major.  Aiyagari_VFI.m (!labor):
+// v_new and the policies are outputs only and are never read.  The labour script (A3): they
+// are in/out — a state without a feasible choice keeps what came in — so they go up first.
+static int vfi_host(bool labor, const double* v_old_cm, const double* a, const double* s,
+                    const double* P, const double* L, int64_t N, int64_t Na, int64_t Nl, double r,
+                    double w, double beta, double sigma, double psi, double eta, bool solve,
+                    double tol, int64_t max_iter, double* v_old_out_cm, double* v_new_cm,
+                    double* pk_cm, double* pl_cm, double* pc_cm, int32_t* idx_cm, int64_t* iters) {
+    if (!v_old_cm || !s || !P || !v_new_cm || !pk_cm || !pc_cm || (labor && (!L || !pl_cm)))
         return fail(AIY_BAD_ARG, "NULL argument");
+    if (labor && (N < 1 || Na < 2 || Nl < 1))
+        return fail(AIY_BAD_SHAPE, "need N >= 1, Na >= 2, Nl >= 1");
     if (N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need N >= 1 and Na >= 2");
     AIY_TRY(check_grid(a, Na));
     std::lock_guard<std::mutex> lk(g_mu);
     HostCtx* c;
-    AIY_TRY(get_ctx(N, Na, 1, &c));
-    double *da, *ds, *dP, *dva, *dvb, *dpk, *dpc;
+    AIY_TRY(get_ctx(N, Na, Nl, &c));
+    const size_t n = (size_t)N * Na;
+    double *da, *ds, *dP, *dva, *dvb, *dpk, *dpc, *dpl = nullptr, *dL = nullptr;
     int* didx;
     AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
-    size_t nb = sizeof(double) * N * Na;
-    AIY_TRY(c->buf("va", nb, (void**)&dva));
-    AIY_TRY(c->buf("vb", nb, (void**)&dvb));
-    AIY_TRY(c->buf("pk", nb, (void**)&dpk));
-    AIY_TRY(c->buf("pc", nb, (void**)&dpc));
-    AIY_TRY(c->buf("idx", sizeof(int) * N * Na, (void**)&didx));
-    std::vector<double> rows(N * Na), tmp(N * Na);
-    cm_to_rows(v_old_cm, N, Na, rows.data());
-    AIY_HIP(hipMemcpyAsync(dva, rows.data(), nb, hipMemcpyHostToDevice, c->st));
-    int out_new = 1;
-    BellCall bc{};
-    bc.a = da; bc.s = ds; bc.P = dP; bc.r = r; bc.w = w; bc.beta = beta; bc.sigma = sigma;
-    bc.idx = didx; bc.pk = dpk; bc.pc = dpc;
-    if (solve) {
-        AIY_TRY(bell_solve_dev(c->ws, bc, dva, dvb, tol, max_iter, iters, &out_new, c->st));
+    AIY_TRY(c->up_rows("va", v_old_cm, N, Na, 1, &dva));
+    if (labor) {
+        AIY_TRY(c->up_rows("vb", v_new_cm, N, Na, 1, &dvb));
+        AIY_TRY(c->up_rows("pk", pk_cm, N, Na, 1, &dpk));
+        AIY_TRY(c->up_rows("pl", pl_cm, N, Na, 1, &dpl));
+        AIY_TRY(c->up_rows("pc", pc_cm, N, Na, 1, &dpc));
+        AIY_TRY(c->up_own("idx", idx_rows0(idx_cm, 1, N, Na), &didx));
+        AIY_TRY(c->up("L", L, (size_t)Nl, &dL));
     } else {
-        bc.v_old = dva;
-        bc.v_new = dvb;
-        AIY_TRY(bell_sweep_dev(c->ws, bc, c->st));
+        AIY_TRY(c->room("vb", n, &dvb));
+        AIY_TRY(c->room("pk", n, &dpk));
+        AIY_TRY(c->room("pc", n, &dpc));
+        AIY_TRY(c->room("idx", n, &didx));
     }
-    double* dnew = out_new ? dvb : dva;
-    double* dold = out_new ? dva : dvb;
-    auto back = [&](const double* d, double* cm) -> int {
-        AIY_HIP(hipMemcpyAsync(tmp.data(), d, nb, hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-        rows_to_cm(tmp.data(), N, Na, cm);
-        return AIY_OK;
-    };
-    AIY_TRY(back(dnew, v_new_cm));
-    AIY_TRY(back(dpk, pk_cm));
-    AIY_TRY(back(dpc, pc_cm));
-    if (solve && v_old_out_cm) AIY_TRY(back(dold, v_old_out_cm));
-    if (idx_cm) {
-        std::vector<int> ib(N * Na);
-        AIY_HIP(hipMemcpyAsync(ib.data(), didx, sizeof(int) * N * Na, hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-        for (int64_t j = 0; j < Na; ++j)
-            for (int64_t i = 0; i < N; ++i) idx_cm[i + j * N] = ib[i * Na + j] + 1;
-    }
-    return AIY_OK;
-}
-
-// A3 host tier: VFI arrays N x Na column-major; v_new and policies in/out.
-static int labor_host(const double* v_old_cm, const double* a, const double* s, const double* P,
-                      const double* L, int64_t N, int64_t Na, int64_t Nl, double r, double w,
-                      double beta, double sigma, double psi, double eta, bool solve, double tol,
-                      int64_t max_iter, double* v_old_out_cm, double* v_new_cm, double* pk_cm,
-                      double* pl_cm, double* pc_cm, int32_t* lin_cm, int64_t* iters) {
-    if (!v_old_cm || !s || !P || !L || !v_new_cm || !pk_cm || !pl_cm || !pc_cm)
-        return fail(AIY_BAD_ARG, "NULL argument");
-    if (N < 1 || Na < 2 || Nl < 1) return fail(AIY_BAD_SHAPE, "need N >= 1, Na >= 2, Nl >= 1");
-    AIY_TRY(check_grid(a, Na));
-    std::lock_guard<std::mutex> lk(g_mu);
-    HostCtx* c;
-    AIY_TRY(get_ctx(N, Na, Nl, &c));
-    double *da, *ds, *dP, *dva, *dvb, *dpk, *dpc, *dpl, *dL;
-    int* dlin;
-    AIY_TRY(stage_common(c, a, s, P, N, Na, &da, &ds, &dP));
-    size_t nb = sizeof(double) * N * Na;
-    AIY_TRY(c->buf("va", nb, (void**)&dva));
-    AIY_TRY(c->buf("vb", nb, (void**)&dvb));
-    AIY_TRY(c->buf("pk", nb, (void**)&dpk));
-    AIY_TRY(c->buf("pc", nb, (void**)&dpc));
-    AIY_TRY(c->buf("pl", nb, (void**)&dpl));
-    AIY_TRY(c->buf("L", sizeof(double) * Nl, (void**)&dL));
-    AIY_TRY(c->buf("idx", sizeof(int) * N * Na, (void**)&dlin));
-    std::vector<double> rows(N * Na), tmp(N * Na);
-    std::vector<int> ib(N * Na);
-    auto up = [&](const double* cm, double* d) -> int {
-        cm_to_rows(cm, N, Na, rows.data());
-        AIY_HIP(hipMemcpyAsync(d, rows.data(), nb, hipMemcpyHostToDevice, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-        return AIY_OK;
-    };
-    AIY_TRY(up(v_old_cm, dva));
-    AIY_TRY(up(v_new_cm, dvb));  // in/out: states without a feasible choice keep these
-    AIY_TRY(up(pk_cm, dpk));
-    AIY_TRY(up(pl_cm, dpl));
-    AIY_TRY(up(pc_cm, dpc));
-    for (int64_t j = 0; j < Na; ++j)
-        for (int64_t i = 0; i < N; ++i) ib[i * Na + j] = lin_cm ? lin_cm[i + j * N] - 1 : 0;
-    AIY_HIP(hipMemcpyAsync(dlin, ib.data(), sizeof(int) * N * Na, hipMemcpyHostToDevice, c->st));
-    AIY_HIP(hipMemcpyAsync(dL, L, sizeof(double) * Nl, hipMemcpyHostToDevice, c->st));
     int out_new = 1;
     BellCall bc{};
-    bc.labor = true; bc.Nl = Nl; bc.L = dL; bc.psi = psi; bc.eta = eta;
+    if (labor) {
+        bc.labor = true; bc.Nl = Nl; bc.L = dL; bc.psi = psi; bc.eta = eta;
+    }
     bc.a = da; bc.s = ds; bc.P = dP; bc.r = r; bc.w = w; bc.beta = beta; bc.sigma = sigma;
-    bc.idx = dlin; bc.pk = dpk; bc.pl = dpl; bc.pc = dpc;
+    bc.idx = didx; bc.pk = dpk; bc.pl = dpl; bc.pc = dpc;
     if (solve) {
-        // the MATLAB loop keeps v_new across sweeps; at sweep 1 the ping-pong partner of
+        // the MATLAB labour loop keeps v_new across sweeps; at sweep 1 the ping-pong partner of
         // v_old must hold the incoming v_new, which merge copies from v_old where needed
         AIY_TRY(bell_solve_dev(c->ws, bc, dva, dvb, tol, max_iter, iters, &out_new, c->st));
     } else {
@@ -215,24 +145,14 @@ static int labor_host(const double* v_old_cm, const double* a, const double* s, 
         bc.v_new = dvb;
         AIY_TRY(bell_sweep_dev(c->ws, bc, c->st));
     }
-    double* dnew = out_new ? dvb : dva;
-    double* dold = out_new ? dva : dvb;
-    auto back = [&](const double* d, double* cm) -> int {
-        AIY_HIP(hipMemcpyAsync(tmp.data(), d, nb, hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-        rows_to_cm(tmp.data(), N, Na, cm);
-        return AIY_OK;
-    };
-    AIY_TRY(back(dnew, v_new_cm));
-    AIY_TRY(back(dpk, pk_cm));
-    AIY_TRY(back(dpl, pl_cm));
-    AIY_TRY(back(dpc, pc_cm));
-    if (solve && v_old_out_cm) AIY_TRY(back(dold, v_old_out_cm));
-    if (lin_cm) {
-        AIY_HIP(hipMemcpyAsync(ib.data(), dlin, sizeof(int) * N * Na, hipMemcpyDeviceToHost, c->st));
-        AIY_HIP(hipStreamSynchronize(c->st));
-        for (int64_t j = 0; j < Na; ++j)
-            for (int64_t i = 0; i < N; ++i) lin_cm[i + j * N] = ib[i * Na + j] + 1;
+    AIY_TRY(c->down_rows(v_new_cm, out_new ? dvb : dva, N, Na, 1));
+    AIY_TRY(c->down_rows(pk_cm, dpk, N, Na, 1));
+    if (labor) AIY_TRY(c->down_rows(pl_cm, dpl, N, Na, 1));
+    AIY_TRY(c->down_rows(pc_cm, dpc, N, Na, 1));
+    if (solve && v_old_out_cm) AIY_TRY(c->down_rows(v_old_out_cm, out_new ? dva : dvb, N, Na, 1));
+    if (idx_cm) {  // back to MATLAB's 1-based index
+        AIY_TRY(c->down_rows(idx_cm, didx, N, Na, 1));
+        for (size_t k = 0; k < n; ++k) idx_cm[k] += 1;
     }
     return AIY_OK;
 }
@@ -266,8 +186,8 @@ int64_t aiy_host_cache_bytes(void) {
 int aiy_vfi_sweep(const double* v_old, const double* a_grid, const double* s, const double* P,
                   int64_t N, int64_t Na, double r, double w, double beta, double sigma,
                   double* v_new, double* policy_k, double* policy_c, int32_t* policy_idx) {
-    return vfi_host(v_old, a_grid, s, P, N, Na, r, w, beta, sigma, false, 0, 1, nullptr, v_new,
-                    policy_k, policy_c, policy_idx, nullptr);
+    return vfi_host(false, v_old, a_grid, s, P, nullptr, N, Na, 1, r, w, beta, sigma, 0, 0, false,
+                    0, 1, nullptr, v_new, policy_k, nullptr, policy_c, policy_idx, nullptr);
 }
 
 int aiy_vfi_solve(double* v_old, const double* a_grid, const double* s, const double* P,
@@ -275,8 +195,8 @@ int aiy_vfi_solve(double* v_old, const double* a_grid, const double* s, const do
                   double tol, int64_t max_iter, double* v_new, double* policy_k,
                   double* policy_c, int32_t* policy_idx, int64_t* iters) {
     if (!iters) return fail(AIY_BAD_ARG, "NULL iters");
-    return vfi_host(v_old, a_grid, s, P, N, Na, r, w, beta, sigma, true, tol, max_iter, v_old,
-                    v_new, policy_k, policy_c, policy_idx, iters);
+    return vfi_host(false, v_old, a_grid, s, P, nullptr, N, Na, 1, r, w, beta, sigma, 0, 0, true,
+                    tol, max_iter, v_old, v_new, policy_k, nullptr, policy_c, policy_idx, iters);
 }
 
 int aiy_labor_vfi_sweep(const double* v_old, const double* a_grid, const double* s,
@@ -284,9 +204,9 @@ int aiy_labor_vfi_sweep(const double* v_old, const double* a_grid, const double*
                         int64_t Nl, double r, double w, double beta, double sigma, double psi,
                         double eta, double* v_new, double* policy_k, double* policy_l,
                         double* policy_c, int32_t* policy_lin) {
-    return labor_host(v_old, a_grid, s, P, labor_choice, N, Na, Nl, r, w, beta, sigma, psi, eta,
-                      false, 0, 1, nullptr, v_new, policy_k, policy_l, policy_c, policy_lin,
-                      nullptr);
+    return vfi_host(true, v_old, a_grid, s, P, labor_choice, N, Na, Nl, r, w, beta, sigma, psi,
+                    eta, false, 0, 1, nullptr, v_new, policy_k, policy_l, policy_c, policy_lin,
+                    nullptr);
 }
 
 int aiy_labor_vfi_solve(double* v_old, const double* a_grid, const double* s, const double* P,
@@ -295,9 +215,9 @@ int aiy_labor_vfi_solve(double* v_old, const double* a_grid, const double* s, co
                         int64_t max_iter, double* v_new, double* policy_k, double* policy_l,
                         double* policy_c, int32_t* policy_lin, int64_t* iters) {
     if (!iters) return fail(AIY_BAD_ARG, "NULL iters");
-    return labor_host(v_old, a_grid, s, P, labor_choice, N, Na, Nl, r, w, beta, sigma, psi, eta,
-                      true, tol, max_iter, v_old, v_new, policy_k, policy_l, policy_c,
-                      policy_lin, iters);
+    return vfi_host(true, v_old, a_grid, s, P, labor_choice, N, Na, Nl, r, w, beta, sigma, psi,
+                    eta, true, tol, max_iter, v_old, v_new, policy_k, policy_l, policy_c, policy_lin,
+                    iters);
 }
 
 }  // extern "C"

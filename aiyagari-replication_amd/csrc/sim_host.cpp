@@ -51,33 +51,31 @@ int aiy_sim_capital(const double* policy_k, int vfi_layout, const double* a_grid
     std::vector<double> s1(N, 1.0);
     double* ds;
     AIY_TRY(stage_common(c, a_grid, s1.data(), P, N, Na, &da, &ds, &dP));
-    size_t nb = sizeof(double) * N * Na;
-    AIY_TRY(c->buf("sim_pol", nb, (void**)&dpol));
-    AIY_TRY(c->buf("sim_U", sizeof(double) * (T > 1 ? T - 1 : 1), (void**)&dU));
-    AIY_TRY(c->buf("sim_out", sizeof(double) + 16, (void**)&dout));
-    AIY_TRY(c->buf("sim_status", sizeof(int) * 4, (void**)&dst));
-    if (sim_k) AIY_TRY(c->buf("sim_k", sizeof(double) * T, (void**)&dk));
-    if (sim_z) AIY_TRY(c->buf("sim_z", sizeof(int) * T, (void**)&dz));
-    AIY_HIP(hipMemcpyAsync(dpol, policy_k, nb, hipMemcpyHostToDevice, c->st));
-    if (T > 1)
-        AIY_HIP(hipMemcpyAsync(dU, uniforms, sizeof(double) * (T - 1), hipMemcpyHostToDevice, c->st));
+    AIY_TRY(c->up("sim_pol", policy_k, (size_t)N * Na, &dpol));
+    if (T > 1) AIY_TRY(c->up("sim_U", uniforms, (size_t)(T - 1), &dU));
+    else AIY_TRY(c->room("sim_U", 1, &dU));
+    AIY_TRY(c->room("sim_out", 3, &dout));
+    AIY_TRY(c->room("sim_status", 4, &dst));
+    if (sim_k) AIY_TRY(c->room("sim_k", (size_t)T, &dk));
+    if (sim_z) AIY_TRY(c->room("sim_z", (size_t)T, &dz));
     // MATLAB layouts: VFI policy_k is N x Na (z stride 1, a stride N); EGM is Na x N.
     size_t zs = vfi_layout ? 1 : (size_t)Na, as = vfi_layout ? (size_t)N : 1;
     double* dks = nullptr;  // the speculative-segment chain's path scratch
-    AIY_TRY(c->buf("sim_kscr", sim_par_scratch_bytes(T, 1), (void**)&dks));
+    AIY_TRY(c->room("sim_kscr", (sim_par_scratch_bytes(T, 1) + sizeof(double) - 1) / sizeof(double),
+                    &dks));
     AIY_TRY(sim_capital_dev(dpol, zs, as, da, dP, N, Na, z1 - 1, k1, T, dU, dout, dk, dz, dst,
                             c->st, false, dks, c->ws ? c->ws->sim_par : -1));
     double out;
     int status;
-    AIY_HIP(hipMemcpyAsync(&out, dout, sizeof(double), hipMemcpyDeviceToHost, c->st));
-    AIY_HIP(hipMemcpyAsync(&status, dst, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    if (sim_k) AIY_HIP(hipMemcpyAsync(sim_k, dk, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    AIY_TRY(c->down(&out, dout, 1));
+    AIY_TRY(c->down(&status, dst, 1));
+    if (sim_k) AIY_TRY(c->down(sim_k, dk, (size_t)T));
     std::vector<int> zb;
     if (sim_z) {
         zb.resize(T);
-        AIY_HIP(hipMemcpyAsync(zb.data(), dz, sizeof(int) * T, hipMemcpyDeviceToHost, c->st));
+        AIY_TRY(c->down(zb.data(), dz, (size_t)T));
     }
-    AIY_HIP(hipStreamSynchronize(c->st));
+    AIY_TRY(c->sync());
     if (status != 0)
         return fail(AIY_FIND_EMPTY, "rand >= cumsum(P(z,:)) for every column: MATLAB's "
                                     "find(...,1) is empty and the assignment at "

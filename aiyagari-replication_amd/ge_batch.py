@@ -182,15 +182,48 @@ def mc_stream(T=10000, steps=10, seed=5489):
     return head, blocks
 
 
+def _stream_start(cal, T):
+    """(z1, k1, blocks) as the scripts draw them from mc_stream(T): z1 = randi(N) (1-based),
+    k1 = a_grid(randi(Na)), then one block of uniforms per simulation."""
+    head, blocks = mc_stream(T)
+    z1 = int(math.ceil(cal["N"] * head[0]))
+    k1 = cal["a_grid"][int(math.ceil(cal["Na"] * head[1])) - 1]
+    return z1, k1, blocks
+
+
+def _with_many(many):
+    """The evaluator that multisection and bisection take, from many(nodes) -> list of results:
+    one node is a batch of one, a round goes through `.many`."""
+    def evaluate(node):
+        return many([node])[0]
+    evaluate.many = many
+    return evaluate
+
+
+def _batch_arrays(r, cal, blocks=None, w=None, ints=(np.int64,)):
+    """What every *_batch_call hands the library, in the layouts it reads: the rates, the wage per
+    rate (w: a scalar or one per rate; None stays None), a_grid, s, P (column-major), the
+    (T-1) x C uniforms matrix of `blocks` (None stays None) and the outputs [K_s, K_d, one array
+    per dtype in `ints`].  Returns (r, w, a, s, P, U, outputs)."""
+    r = np.ascontiguousarray(r, np.float64)
+    n = r.size
+    if w is not None:
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
+    U = None
+    if blocks is not None:
+        U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
+    a = np.ascontiguousarray(cal["a_grid"], np.float64)
+    s = np.ascontiguousarray(cal["s"], np.float64)
+    P = np.asfortranarray(cal["P"], dtype=np.float64)
+    return r, w, a, s, P, U, [np.empty(n), np.empty(n)] + [np.empty(n, t) for t in ints]
+
+
 def vfi_evaluator(cal, solve, simulate, v_start, T=10000, tol=1e-5, max_iter=1000):
     """Node evaluator for Aiyagari_VFI.m: VFI from v_start (path-independent warm start), MC
     supply with the uniforms block of the node's depth, K_d (:195).
     solve(v_old, r, w) -> dict(policy_k, iters); simulate(policy_k, z1, k1, uniforms) -> K_s."""
     from . import calibration as cb
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
+    z1, k1, blocks = _stream_start(cal, T)
 
     def evaluate(node):
         r = node.r
@@ -218,22 +251,14 @@ def hip_vfi_evaluator(cal, v_start, T=10000, tol=1e-5, max_iter=1000):
 def ge_batch_call(r, v_start, cal, z1, k1, blocks, tol=1e-5, max_iter=1000, n_devices=1):
     """aiy_ge_batch (C ABI): K_s, K_d and iteration count at every rate in `r`, each
     from v_start, with uniforms blocks[c] (T-1 draws) for candidate c; z1 1-based."""
-    import ctypes as C
     from ._capi import check, d, i64, ip, lib, ptr
-    r = np.ascontiguousarray(r, np.float64)
-    n = r.size
-    N, Na = cal["N"], cal["Na"]
-    U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
-    T = U.shape[0] + 1
+    r, _, a, s, P, U, (Ks, Kd, it) = _batch_arrays(r, cal, blocks)
     v = np.asfortranarray(v_start, dtype=np.float64)
-    a = np.ascontiguousarray(cal["a_grid"], np.float64)
-    s = np.ascontiguousarray(cal["s"], np.float64)
-    P = np.asfortranarray(cal["P"], dtype=np.float64)
-    Ks, Kd, it = np.empty(n), np.empty(n), np.empty(n, np.int64)
-    check(lib().aiy_ge_batch(ptr(r), i64(n), ptr(v), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
-                             d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]), d(cal["sigma"]),
-                             d(cal["labor"]), d(tol), i64(max_iter), i64(z1), d(k1), i64(T),
-                             ptr(U), ip(n_devices), ptr(Ks), ptr(Kd), ptr(it)))
+    check(lib().aiy_ge_batch(ptr(r), i64(r.size), ptr(v), ptr(a), ptr(s), ptr(P), i64(cal["N"]),
+                             i64(cal["Na"]), d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
+                             d(cal["sigma"]), d(cal["labor"]), d(tol), i64(max_iter), i64(z1),
+                             d(k1), i64(U.shape[0] + 1), ptr(U), ip(n_devices), ptr(Ks), ptr(Kd),
+                             ptr(it)))
     return Ks, Kd, it
 
 
@@ -241,20 +266,13 @@ def hip_batch_evaluator(cal, v_start, T=10000, tol=1e-5, max_iter=1000, n_device
     """The node evaluator on the batched device path: all of a round's nodes of this rank in
     one aiy_ge_batch call (one batched solve and one batched launch of the chains per GPU).
     Same per-node arithmetic as vfi_evaluator, so the traces are identical."""
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
+    z1, k1, blocks = _stream_start(cal, T)
 
     def many(nodes):
         Ks, Kd, it = ge_batch_call([n.r for n in nodes], v_start, cal, z1, k1,
                                    [blocks[n.depth] for n in nodes], tol, max_iter, n_devices)
         return [(float(Ks[q]), float(Kd[q]), int(it[q])) for q in range(len(nodes))]
-
-    def evaluate(node):
-        return many([node])[0]
-    evaluate.many = many
-    return evaluate
+    return _with_many(many)
 
 
 def auto_levels(world: int) -> int:
@@ -310,10 +328,7 @@ def egm_evaluator(cal, solve, simulate, pc_start, w, labor=False, T=10000):
     simulate(policy_k, z1, k1, uniforms) -> K_s.  `labor` only documents which script the
     callables restate.  Results are (K_s, K_d, iters, status); K_s is NaN where status != 0."""
     from . import calibration as cb
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
+    z1, k1, blocks = _stream_start(cal, T)
 
     def evaluate(node):
         R = solve(pc_start, node.r, w)
@@ -324,25 +339,33 @@ def egm_evaluator(cal, solve, simulate, pc_start, w, labor=False, T=10000):
     return evaluate
 
 
-def hip_egm_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, max_iter=1000, phi=1.0,
-                      theta=1.0):
-    """The evaluator on this rank's GPU, one solve after another (host tier); pc_start [N][Na]."""
+def _hip_egm_solve(cal, labor, tol, max_iter, phi, theta):
+    """solve(pc [N][Na], r, w) -> the host tier's EGM solve of the script `labor` names; where it
+    refuses an endogenous grid that is not increasing, dict(policy_k=None, iters=0, status=1)."""
     from ._capi import AiyError
     from .egm import egm_solve, labor_egm_solve
-    from .sim import sim_capital
     a, s, P = cal["a_grid"], cal["s"], cal["P"]
 
-    def solve(pc, r, w_):
+    def solve(pc, r, w):
         try:
             if labor:
-                return labor_egm_solve(pc.T, a, s, P, r, w_, cal["beta"], cal["sigma"], phi, theta,
+                return labor_egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], phi, theta,
                                        cal["amin"], tol, max_iter)
-            return egm_solve(pc.T, a, s, P, r, w_, cal["beta"], cal["sigma"], cal["amin"], tol,
+            return egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], cal["amin"], tol,
                              max_iter)
         except AiyError as e:
             if "not increasing" not in str(e):
                 raise
             return dict(policy_k=None, iters=0, status=1)
+    return solve
+
+
+def hip_egm_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, max_iter=1000, phi=1.0,
+                      theta=1.0):
+    """The evaluator on this rank's GPU, one solve after another (host tier); pc_start [N][Na]."""
+    from .sim import sim_capital
+    a, P = cal["a_grid"], cal["P"]
+    solve = _hip_egm_solve(cal, labor, tol, max_iter, phi, theta)
 
     def simulate(pk, z1, k1, u):
         return sim_capital(pk, a, P, z1, k1, u, vfi_layout=False)
@@ -355,20 +378,11 @@ def egm_ge_batch_call(r, w, pc_start, cal, z1, k1, blocks, labor=False, phi=1.0,
     from pc_start ([N][Na]) at wage w (a scalar or one per rate), with uniforms blocks[c]
     (T-1 draws) for candidate c; z1 1-based."""
     from ._capi import check, d, i64, ip, lib, ptr
-    r = np.ascontiguousarray(r, np.float64)
-    n = r.size
-    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
-    N, Na = cal["N"], cal["Na"]
-    U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
-    T = U.shape[0] + 1
+    r, w, a, s, P, U, (Ks, Kd, it, st) = _batch_arrays(r, cal, blocks, w, (np.int64, np.int32))
+    n, N, Na, T = r.size, cal["N"], cal["Na"], U.shape[0] + 1
     pc = np.ascontiguousarray(pc_start, np.float64)  # [N][Na] == the script's Na x N
     if pc.shape != (N, Na):
         raise ValueError(f"pc_start must be [N][Na] = {(N, Na)}")
-    a = np.ascontiguousarray(cal["a_grid"], np.float64)
-    s = np.ascontiguousarray(cal["s"], np.float64)
-    P = np.asfortranarray(cal["P"], dtype=np.float64)
-    Ks, Kd = np.empty(n), np.empty(n)
-    it, st = np.empty(n, np.int64), np.empty(n, np.int32)
     check(lib().aiy_egm_ge_batch(ptr(r), ptr(w), i64(n), ptr(pc), ptr(a), ptr(s), ptr(P), i64(N),
                                  i64(Na), d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
                                  d(cal["sigma"]), d(cal["amin"]), ip(1 if labor else 0), d(phi),
@@ -383,21 +397,14 @@ def hip_egm_batch_evaluator(cal, pc_start, w, labor=False, T=10000, tol=1e-5, ma
     """The node evaluator on the batched device path: all of a round's nodes of this rank in
     one aiy_egm_ge_batch call (one launch of the solves and one of the chains per GPU).  Same
     per-node arithmetic as hip_egm_evaluator, so the traces are identical."""
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
+    z1, k1, blocks = _stream_start(cal, T)
 
     def many(nodes):
         Ks, Kd, it, st = egm_ge_batch_call([n.r for n in nodes], w, pc_start, cal, z1, k1,
                                            [blocks[n.depth] for n in nodes], labor, phi, theta,
                                            tol, max_iter, n_devices)
         return [(float(Ks[q]), float(Kd[q]), int(it[q]), int(st[q])) for q in range(len(nodes))]
-
-    def evaluate(node):
-        return many([node])[0]
-    evaluate.many = many
-    return evaluate
+    return _with_many(many)
 
 
 def aiyagari_egm_multisection(Na=400, labor=False, levels=None, rank=0, world=1, allgather=None,
@@ -486,29 +493,16 @@ def hip_egm_hist_evaluator(cal, pc_start, w, labor=False, tol=1e-5, max_iter=100
                            theta=1.0):
     """hist_evaluator on this rank's GPU for the EGM scripts (pc_start, lam_start [N][Na]), one
     solve and one lottery histogram after another."""
-    from ._capi import AiyError
     from .dist import dist_stationary
-    from .egm import egm_solve, labor_egm_solve
-    a, s, P = cal["a_grid"], cal["s"], cal["P"]
-
-    def solve(pc, r):
-        try:
-            if labor:
-                return labor_egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], phi, theta,
-                                       cal["amin"], tol, max_iter)
-            return egm_solve(pc.T, a, s, P, r, w, cal["beta"], cal["sigma"], cal["amin"], tol,
-                             max_iter)
-        except AiyError as e:
-            if "not increasing" not in str(e):
-                raise
-            return dict(policy_k=None, iters=0, status=1)
+    a, P = cal["a_grid"], cal["P"]
+    solve = _hip_egm_solve(cal, labor, tol, max_iter, phi, theta)
 
     def supply(R):
         _, K, it, _ = dist_stationary(a, P, policy_k=R["policy_k"],
                                       lam0=None if lam_start is None else np.asarray(lam_start).T,
                                       tol=dist_tol, max_iter=dist_max_iter, vfi_layout=False)
         return K, it
-    return hist_evaluator(cal, solve, supply, pc_start)
+    return hist_evaluator(cal, lambda pc, r: solve(pc, r, w), supply, pc_start)
 
 
 def ge_hist_batch_call(r, v_start, cal, tol=1e-5, max_iter=1000, dist_tol=HIST_TOL,
@@ -516,18 +510,12 @@ def ge_hist_batch_call(r, v_start, cal, tol=1e-5, max_iter=1000, dist_tol=HIST_T
     """aiy_ge_hist_batch (C ABI): K_s (histogram), K_d, VFI sweeps and pushes at every rate in
     `r`, each from v_start and lam_start (N x Na; None: uniform)."""
     from ._capi import check, d, i64, ip, lib, ptr
-    r = np.ascontiguousarray(r, np.float64)
-    n = r.size
-    N, Na = cal["N"], cal["Na"]
+    r, _, a, s, P, _, (Ks, Kd, it, dit) = _batch_arrays(r, cal, ints=(np.int64, np.int64))
+    n, N, Na = r.size, cal["N"], cal["Na"]
     v = np.asfortranarray(v_start, dtype=np.float64)
     lam = None if lam_start is None else np.asfortranarray(lam_start, dtype=np.float64)
     if lam is not None and lam.shape != (N, Na):
         raise ValueError(f"lam_start must be (N, Na) = {(N, Na)}")
-    a = np.ascontiguousarray(cal["a_grid"], np.float64)
-    s = np.ascontiguousarray(cal["s"], np.float64)
-    P = np.asfortranarray(cal["P"], dtype=np.float64)
-    Ks, Kd = np.empty(n), np.empty(n)
-    it, dit = np.empty(n, np.int64), np.empty(n, np.int64)
     check(lib().aiy_ge_hist_batch(ptr(r), i64(n), ptr(v), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
                                   d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
                                   d(cal["sigma"]), d(cal["labor"]), d(tol), i64(max_iter),
@@ -543,19 +531,13 @@ def egm_ge_hist_batch_call(r, w, pc_start, cal, labor=False, phi=1.0, theta=1.0,
     at every rate in `r`, each from pc_start and lam_start ([N][Na]; None: uniform) at wage w
     (a scalar or one per rate)."""
     from ._capi import check, d, i64, ip, lib, ptr
-    r = np.ascontiguousarray(r, np.float64)
-    n = r.size
-    w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float64), (n,)))
-    N, Na = cal["N"], cal["Na"]
+    r, w, a, s, P, _, (Ks, Kd, it, dit, st) = _batch_arrays(
+        r, cal, w=w, ints=(np.int64, np.int64, np.int32))
+    n, N, Na = r.size, cal["N"], cal["Na"]
     pc = np.ascontiguousarray(pc_start, np.float64)  # [N][Na] == the script's Na x N
     lam = None if lam_start is None else np.ascontiguousarray(lam_start, np.float64)
     if pc.shape != (N, Na) or (lam is not None and lam.shape != (N, Na)):
         raise ValueError(f"pc_start and lam_start must be [N][Na] = {(N, Na)}")
-    a = np.ascontiguousarray(cal["a_grid"], np.float64)
-    s = np.ascontiguousarray(cal["s"], np.float64)
-    P = np.asfortranarray(cal["P"], dtype=np.float64)
-    Ks, Kd = np.empty(n), np.empty(n)
-    it, dit, st = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.int32)
     check(lib().aiy_egm_ge_hist_batch(ptr(r), ptr(w), i64(n), ptr(pc), ptr(a), ptr(s), ptr(P),
                                       i64(N), i64(Na), d(cal["alpha"]), d(cal["delta"]),
                                       d(cal["beta"]), d(cal["sigma"]), d(cal["amin"]),
@@ -576,11 +558,7 @@ def hip_hist_batch_evaluator(cal, v_start, tol=1e-5, max_iter=1000, dist_tol=HIS
                                              dist_tol, dist_max_iter, lam_start, n_devices)
         return [(float(Ks[q]), float(Kd[q]), int(it[q]), 0, int(dit[q]))
                 for q in range(len(nodes))]
-
-    def evaluate(node):
-        return many([node])[0]
-    evaluate.many = many
-    return evaluate
+    return _with_many(many)
 
 
 def hip_egm_hist_batch_evaluator(cal, pc_start, w, labor=False, tol=1e-5, max_iter=1000,
@@ -594,11 +572,7 @@ def hip_egm_hist_batch_evaluator(cal, pc_start, w, labor=False, tol=1e-5, max_it
                                                      dist_max_iter, lam_start, n_devices)
         return [(float(Ks[q]), float(Kd[q]), int(it[q]), int(st[q]), int(dit[q]))
                 for q in range(len(nodes))]
-
-    def evaluate(node):
-        return many([node])[0]
-    evaluate.many = many
-    return evaluate
+    return _with_many(many)
 
 
 # ------------------------------------------------------- the labour VFI script (E2)
@@ -622,20 +596,9 @@ def labor_vfi_evaluator(cal, solve, simulate, start, T=10000):
     (labor_start: the path-independent warm start) at the node's r and its own wage, MC supply on
     policy_k with the uniforms block of the node's depth, K_d.  Generic in the two callables (the
     GPU path or the C oracle): solve(start, r, w) -> dict(policy_k, iters);
-    simulate(policy_k, z1, k1, uniforms) -> K_s."""
-    from . import calibration as cb
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
-
-    def evaluate(node):
-        r = node.r
-        R = solve(start, r, cb.wage(r, cal["alpha"], cal["delta"]))
-        Ks = simulate(R["policy_k"], z1, k1, blocks[node.depth])
-        Kd = cb.capital_demand(r, cal["labor"], cal["alpha"], cal["delta"])
-        return (float(Ks), float(Kd), int(R["iters"]))
-    return evaluate
+    simulate(policy_k, z1, k1, uniforms) -> K_s.  The steps are vfi_evaluator's, with the
+    labour script's state as the start."""
+    return vfi_evaluator(cal, solve, simulate, start, T)
 
 
 def hip_labor_vfi_evaluator(cal, L, start, T=10000, tol=1e-5, max_iter=1000, psi=1.0, eta=2.0):
@@ -659,11 +622,8 @@ def labor_ge_batch_call(r, start, cal, L, z1, k1, blocks, psi=1.0, eta=2.0, tol=
     `start` (labor_start; v_new / policies None = zeros), with uniforms blocks[c] (T-1 draws) for
     candidate c; z1 1-based."""
     from ._capi import check, d, i64, ip, lib, ptr
-    r = np.ascontiguousarray(r, np.float64)
-    n = r.size
-    N, Na = cal["N"], cal["Na"]
-    U = np.asfortranarray(np.stack([np.asarray(b, np.float64) for b in blocks], axis=1))
-    T = U.shape[0] + 1
+    r, _, a, s, P, U, (Ks, Kd, it) = _batch_arrays(r, cal, blocks)
+    n, N, Na, T = r.size, cal["N"], cal["Na"], U.shape[0] + 1
     f = lambda x: None if x is None else np.asfortranarray(x, dtype=np.float64)
     v, vn = f(start["v_old"]), f(start.get("v_new"))
     pol = start.get("policies") or (None, None, None, None)
@@ -672,11 +632,7 @@ def labor_ge_batch_call(r, start, cal, L, z1, k1, blocks, psi=1.0, eta=2.0, tol=
     for x in (v, vn, pk, pl, pc, lin):
         if x is not None and x.shape != (N, Na):
             raise ValueError(f"start arrays must be (N, Na) = {(N, Na)}")
-    a = np.ascontiguousarray(cal["a_grid"], np.float64)
-    s = np.ascontiguousarray(cal["s"], np.float64)
-    P = np.asfortranarray(cal["P"], dtype=np.float64)
     L = np.ascontiguousarray(L, np.float64)
-    Ks, Kd, it = np.empty(n), np.empty(n), np.empty(n, np.int64)
     check(lib().aiy_labor_ge_batch(ptr(r), i64(n), ptr(v), ptr(vn), ptr(pk), ptr(pl), ptr(pc),
                                    ptr(lin), ptr(a), ptr(s), ptr(P), ptr(L), i64(N), i64(Na),
                                    i64(L.size), d(cal["alpha"]), d(cal["delta"]), d(cal["beta"]),
@@ -691,21 +647,14 @@ def hip_labor_batch_evaluator(cal, L, start, T=10000, tol=1e-5, max_iter=1000, n
     """The node evaluator on the batched device path: all of a round's nodes of this rank in one
     aiy_labor_ge_batch call (one launch per sweep over all of them, one launch of the chains per
     GPU).  Same per-node arithmetic as hip_labor_vfi_evaluator, so the traces are identical."""
-    N, Na, a = cal["N"], cal["Na"], cal["a_grid"]
-    head, blocks = mc_stream(T)
-    z1 = int(math.ceil(N * head[0]))
-    k1 = a[int(math.ceil(Na * head[1])) - 1]
+    z1, k1, blocks = _stream_start(cal, T)
 
     def many(nodes):
         Ks, Kd, it = labor_ge_batch_call([n.r for n in nodes], start, cal, L, z1, k1,
                                          [blocks[n.depth] for n in nodes], psi, eta, tol,
                                          max_iter, n_devices)
         return [(float(Ks[q]), float(Kd[q]), int(it[q])) for q in range(len(nodes))]
-
-    def evaluate(node):
-        return many([node])[0]
-    evaluate.many = many
-    return evaluate
+    return _with_many(many)
 
 
 # tree levels per round on one GPU (measured: DESIGN.md §5, profiles/r10_labor_batch_ab.txt)

@@ -110,5 +110,6 @@ def test_devbuf_edge_cases(tmp_path):
 
 
 def test_host_ctx_named_buffers(tmp_path):
-    """The host tier's name -> buffer map (csrc/host_ctx.hpp) on malloc-backed memory."""
+    """The host tier's name -> buffer map and its typed staging (broadcast, layout helpers; csrc/
+    host_ctx.hpp) on malloc-backed memory."""
     _run_hip_host_program(tmp_path, "host_ctx_main.cpp")
