@@ -27,25 +27,6 @@
 
 namespace aiy {
 
-// interp1(â_j, y_j, q, 'linear', 'extrap') on the LDS row: the count by binary search, the
-// segment clamp(count, 1, Na−1) − 1 and the formula of egm_fused_kernel
-__device__ __forceinline__ double egm_batch_interp(const double* __restrict__ x,
-                                                   const double* __restrict__ y, int Na,
-                                                   double q) {
-    int lo = 0, hi = Na;  // #{k : â_k <= q}
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (x[mid] <= q) lo = mid + 1;
-        else hi = mid;
-    }
-    int sgi = lo - 1;
-    sgi = sgi < 0 ? 0 : sgi;
-    sgi = sgi > Na - 2 ? Na - 2 : sgi;
-    const double x0 = x[sgi], x1 = x[sgi + 1];
-    const double tt = (q - x0) / (x1 - x0);
-    return y[sgi] + tt * (y[sgi + 1] - y[sgi]);
-}
-
 template <bool LAB>
 __global__ __launch_bounds__(1024) void egm_solve_batch_kernel(EgmBatchArgs A) {
     extern __shared__ __align__(16) unsigned char egm_batch_lds[];

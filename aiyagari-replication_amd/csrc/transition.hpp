@@ -1,0 +1,65 @@
+// Launch interface of the transition-path kernels (transition_kernels.hip): the backward EGM pass
+// and the forward histogram pass of a perfect-foresight (MIT shock) transition, C price paths per
+// launch, one workgroup per path.  Arrays [C][...] hold path c's block at c · (the block's size).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dist.hpp"
+#include "egm.hpp"
+
+namespace aiy {
+
+// The backward pass: from pc_T, t = T−1 … 0, the two-rate EGM step
+//   RHS(j,a) = Σ_m ((β(1+r[t+1]))·P(j,m))·u'(pc_{t+1}(m,a)),  c̃ = RHS^(−1/σ),
+//   â = ((c̃ + a) − w[t]·s_j)/(1 + r[t]),  g = interp1(â_j, a, a),  g < amin → amin,
+//   pk_t = g,  pc_t = ((1 + r[t])·a + w[t]·s_j) − g
+// — egm_fused_kernel's operations with r split into r[t+1] (the Euler equation) and r[t].
+struct EgmBackwardArgs {
+    int N, Na, C, T;
+    int ns;  // as EgmArgs
+    double beta, sigma, amin;
+    const double* r;    // device [C][T+1]; r[c][T] is the terminal rate
+    const double* w;    // device [C][T]
+    const double* pcT;  // device [C][N][Na], or one [N][Na] for every path (pcT_stride = 0)
+    size_t pcT_stride;  // N·Na or 0
+    const double* a;
+    const double* s;
+    const double* P;
+    double* pk;   // device [C][T][N][Na]
+    double* pc;   // device [C][T][N][Na] (nullable)
+    int* status;  // device [C]: 0 ok, 1 = â not increasing at period fail_t (periods below it
+                  // are not computed; the period's own outputs are undefined)
+    int* fail_t;  // device [C]: −1, or the period that stopped the path
+};
+inline bool egm_backward_fits(int64_t N, int64_t Na) { return egm_batch_fits(N, Na, false); }
+int launch_egm_backward_batch(const EgmBackwardArgs& A, hipStream_t st);
+
+// The forward pass: from λ₀, t = 0 … T−1: the lottery plan of pk_t, K[t] = Σ λ_t·a, one push.
+struct DistForwardArgs {
+    int N, Na, C, T;
+    const double* pk;    // device [C][T][N][Na]
+    const double* lam0;  // device [C][N][Na], or one [N][Na] for every path (lam0_stride = 0)
+    size_t lam0_stride;  // N·Na or 0
+    const double* a;
+    const double* P;     // row-major
+    double* K;           // device [C][T+1]
+    double* lamT;        // device [C][N][Na] (nullable)
+    int* status;         // device [C]: 0 ok, 2 = pk_t's keys not monotone at period fail_t (K up
+                         // to fail_t is written, the rest NaN, lamT = λ at fail_t)
+    int* fail_t;         // device [C]
+    const int* skip;     // device [C] (nullable): a non-zero entry — the backward pass's status —
+                         // leaves the path alone but for K, all NaN; status and fail_t not written
+};
+// LDS of one workgroup: dist_solve_batch_kernel<true>'s (λ, mass, lottery weights, run offsets,
+// scratch) and a_grid.  The period's keys and the partial sums of K live in the mass array, which
+// is dead while the plan is built.
+inline size_t dist_forward_lds_bytes(int64_t N, int64_t Na) {
+    return dist_batch_lds_bytes(N, Na, true) + sizeof(double) * (size_t)Na;
+}
+// dist_batch_fits for the lottery case, with a_grid's Na doubles on top
+inline bool dist_forward_fits(int64_t N, int64_t Na) {
+    return dist_batch_fits(N, Na, true) && dist_forward_lds_bytes(N, Na) <= kDistBatchMaxLds;
+}
+int launch_dist_forward_batch(const DistForwardArgs& A, hipStream_t st);
+
+}  // namespace aiy

@@ -68,6 +68,20 @@ struct LaborBatchBlocks {
     PinnedBuf<int> hstop;   // [C]
     PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
 };
+// transition passes (aiy_egm_backward_batch_dev, aiy_dist_forward_batch_dev): the paths' prices
+// and per-path results on the device and their pinned copies, sized for the largest call seen
+struct TransitionBlocks {
+    DevBuf<double> rw;       // device [C][T+1] r, then [C][T] w
+    DevBuf<int> res;         // device [2][C]: status, fail_t
+    PinnedBuf<double> hrw;
+    PinnedBuf<int> hres;
+    int ensure(size_t C, size_t T) {  // (the entries bound C and T below 2^31: no overflow)
+        AIY_TRY(rw.ensure(C * (2 * T + 1)));
+        AIY_TRY(res.ensure(2 * C));
+        AIY_TRY(hrw.ensure(C * (2 * T + 1)));
+        return hres.ensure(2 * C);
+    }
+};
 }  // namespace aiy
 
 struct aiy_ws {
@@ -162,6 +176,7 @@ struct aiy_ws {
     int dist_batch_min = -1;
     aiy::DistBatchBlocks dist_batch;
     int64_t dist_batch_launches = 0, dist_batch_fallbacks = 0;
+    aiy::TransitionBlocks transition;
     // timing of the dominant kernel
     bool timing = false, count_hits = false;
     aiy::Events ev_start, ev_stop;

@@ -1,0 +1,218 @@
+"""Perfect-foresight transition paths of the Aiyagari EGM economy (MIT shocks) on the GPU.
+
+A transition is two passes over T periods.  The backward pass takes a price path (r_t, w_t) and
+iterates the two-rate EGM step back from the terminal steady-state policy; the forward pass
+pushes the initial distribution through the period policies and yields the capital path K_t.
+C paths run per call, one workgroup per path and pass (include/aiyagari_hip.h, "Transition
+paths").  Arrays are [N][Na] rows per (path, period), C-contiguous: policy_k [C][T][N][Na]."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from ._capi import check, d, i64, ip, lib, ptr
+
+
+def _f(x):
+    return np.ascontiguousarray(x, np.float64)
+
+
+def _paths(r, w):
+    r, w = np.atleast_2d(_f(r)), np.atleast_2d(_f(w))
+    if r.ndim != 2 or w.ndim != 2 or r.shape != (w.shape[0], w.shape[1] + 1):
+        raise ValueError("r must be [C][T+1] and w [C][T]")
+    return r, w, w.shape[0], w.shape[1]
+
+
+def _start(x, n_c, N, Na, name):
+    """A start array shared by all paths ([N][Na]) or one per path ([C][N][Na]) -> (array, flag)."""
+    x = _f(x)
+    if x.shape == (N, Na):
+        return x, 1
+    if x.shape == (n_c, N, Na):
+        return x, 0
+    raise ValueError(f"{name} must be [N][Na] = {(N, Na)} or [C][N][Na]")
+
+
+def egm_backward_batch(r, w, pc_T, a_grid, s, P, beta, sigma, amin, want_pc=True):
+    """aiy_egm_backward_batch: r [C][T+1] (r[c][T]: the terminal rate), w [C][T], pc_T [N][Na]
+    (shared) or [C][N][Na].  Returns dict(policy_k, policy_c [C][T][N][Na] (None unless want_pc),
+    status [C], fail_t [C]); status 1: the endogenous grid of period fail_t was not increasing
+    (that path's periods <= fail_t are undefined, the other paths are unaffected)."""
+    r, w, n_c, T = _paths(r, w)
+    a, s, P = _f(a_grid), _f(s), np.asfortranarray(P, dtype=np.float64)
+    N, Na = s.size, a.size
+    pcT, shared = _start(pc_T, n_c, N, Na, "pc_T")
+    pk = np.empty((n_c, T, N, Na))
+    pc = np.empty((n_c, T, N, Na)) if want_pc else None
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_egm_backward_batch(i64(n_c), i64(T), ptr(r), ptr(w), ptr(pcT), ip(shared),
+                                       ptr(a), ptr(s), ptr(P), i64(N), i64(Na), d(beta), d(sigma),
+                                       d(amin), ptr(pk), ptr(pc), ptr(st), ptr(ft)))
+    return dict(policy_k=pk, policy_c=pc, status=st, fail_t=ft)
+
+
+def dist_forward_batch(policy_k, lam0, a_grid, P, want_lam=True):
+    """aiy_dist_forward_batch: policy_k [C][T][N][Na], lam0 [N][Na] (shared) or [C][N][Na].
+    Returns dict(K [C][T+1], lam_T [C][N][Na] (None unless want_lam), status [C], fail_t [C]);
+    status 2: the keys of policy_k[c][fail_t] are not monotone (K beyond fail_t is NaN)."""
+    pk = _f(policy_k)
+    if pk.ndim != 4:
+        raise ValueError("policy_k must be [C][T][N][Na]")
+    n_c, T, N, Na = pk.shape
+    a, P = _f(a_grid), np.asfortranarray(P, dtype=np.float64)
+    l0, shared = _start(lam0, n_c, N, Na, "lam0")
+    K = np.empty((n_c, T + 1))
+    lT = np.empty((n_c, N, Na)) if want_lam else None
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_dist_forward_batch(i64(n_c), i64(T), ptr(pk), ptr(l0), ip(shared), ptr(a),
+                                       ptr(P), i64(N), i64(Na), ptr(K), ptr(lT), ptr(st), ptr(ft)))
+    return dict(K=K, lam_T=lT, status=st, fail_t=ft)
+
+
+def transition_batch(r, w, pc_T, lam0, a_grid, s, P, beta, sigma, amin):
+    """aiy_transition_batch: both passes on one stream, the period policies staying on the device.
+    Returns (K [C][T+1], status [C], fail_t [C]); a path with status 1 has K all NaN."""
+    r, w, n_c, T = _paths(r, w)
+    a, s, P = _f(a_grid), _f(s), np.asfortranarray(P, dtype=np.float64)
+    N, Na = s.size, a.size
+    pcT, pshared = _start(pc_T, n_c, N, Na, "pc_T")
+    l0, lshared = _start(lam0, n_c, N, Na, "lam0")
+    K = np.empty((n_c, T + 1))
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_transition_batch(i64(n_c), i64(T), ptr(r), ptr(w), ptr(pcT), ip(pshared),
+                                     ptr(l0), ip(lshared), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
+                                     d(beta), d(sigma), d(amin), ptr(K), ptr(st), ptr(ft)))
+    return K, st, ft
+
+
+def egm_backward_batch_dev(ws, r, w, pc_T, a_grid, s, P, beta, sigma, amin, policy_k,
+                           policy_c=None, stream=None):
+    """aiy_egm_backward_batch_dev (torch tensors; r [C][T+1] and w [C][T] numpy): pc_T [N][Na]
+    (shared) or [C][N][Na]; policy_k, policy_c (optional): [C][T][N][Na]; P row-major.
+    Returns (status [C], fail_t [C]) as numpy arrays."""
+    from ._capi import stream_handle
+    r, w, n_c, T = _paths(r, w)
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_egm_backward_batch_dev(ws.handle, i64(n_c), i64(T), ptr(r), ptr(w), ptr(pc_T),
+                                           ip(1 if pc_T.dim() == 2 else 0), ptr(a_grid), ptr(s),
+                                           ptr(P), d(beta), d(sigma), d(amin), ptr(policy_k),
+                                           ptr(policy_c), ptr(st), ptr(ft), stream_handle(stream)))
+    return st, ft
+
+
+def dist_forward_batch_dev(ws, policy_k, lam0, a_grid, P, K, lam_T=None, stream=None):
+    """aiy_dist_forward_batch_dev (torch tensors): policy_k [C][T][N][Na], lam0 [N][Na] (shared)
+    or [C][N][Na], K [C][T+1], lam_T (optional) [C][N][Na]; P row-major.
+    Returns (status [C], fail_t [C]) as numpy arrays."""
+    from ._capi import stream_handle
+    n_c, T = int(policy_k.shape[0]), int(policy_k.shape[1])
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_dist_forward_batch_dev(ws.handle, i64(n_c), i64(T), ptr(policy_k), ptr(lam0),
+                                           ip(1 if lam0.dim() == 2 else 0), ptr(a_grid), ptr(P),
+                                           ptr(K), ptr(lam_T), ptr(st), ptr(ft),
+                                           stream_handle(stream)))
+    return st, ft
+
+
+def prices_from_K(K, Z, ss):
+    """The price paths of capital paths K and TFP paths Z (same shape), anchored to the steady
+    state ss (r, w, K; alpha, delta in ss["cal"]):
+        r_t + δ = (r_ss + δ)·Z_t·(K_t/K_ss)^(α−1),   w_t = w_ss·Z_t·(K_t/K_ss)^α.
+    At K = K_ss, Z = 1 this returns r_ss and w_ss exactly, whatever residual the steady state's
+    bisection left between K_ss and the capital demand at r_ss."""
+    K, Z = np.asarray(K, np.float64), np.asarray(Z, np.float64)
+    alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]
+    x = K / ss["K"]
+    # r_ss + (r_ss + δ)·(Z·x^(α−1) − 1): the same rate, and exactly r_ss at the stationary point
+    r = ss["r"] + (ss["r"] + delta) * (Z * _pow(x, alpha - 1) - 1.0)
+    return r, ss["w"] * Z * _pow(x, alpha)
+
+
+def _pow(x, p):
+    """x ** p element by element through math.pow: an element's result does not depend on its
+    place in the array (a vectorised power may treat a block's tail differently), which keeps a
+    path's arithmetic independent of its batch."""
+    return np.array([math.pow(v, p) for v in x.ravel()]).reshape(x.shape)
+
+
+def steady_state(cal, r_low=-0.02, r_high=None, steps=40, levels=3, tol=1e-5, max_iter=1000,
+                 k_tol=1e-8):
+    """The stationary equilibrium a transition starts from and returns to: dict(r, w, K,
+    policy_c, lam ([N][Na]), cal).  r by bisection on the lottery-histogram capital supply, a
+    round's candidates in one aiy_egm_ge_hist_batch call (ge_batch.egm_ge_hist_batch_call), each
+    at its own wage cb.wage(r) — not the EGM script's frozen wage; then policy_c from egm_solve
+    and λ, K from dist_stationary at that r."""
+    from . import calibration as cb
+    from . import ge_batch as gb
+    from .dist import dist_stationary
+    from .egm import egm_solve
+    a, s, P = cal["a_grid"], cal["s"], cal["P"]
+    wage = lambda r: cb.wage(r, cal["alpha"], cal["delta"])
+    r0 = 0.04
+    guess = np.tile((1 + r0) * a + wage(r0) * np.mean(s), (cal["N"], 1))
+
+    def many(nodes):
+        rr = np.array([n.r for n in nodes])
+        Ks, Kd, it, dit, st = gb.egm_ge_hist_batch_call(rr, wage(rr), guess, cal, tol=tol,
+                                                        max_iter=max_iter)
+        return [(float(Ks[q]), float(Kd[q]), int(it[q]), int(st[q]), int(dit[q]))
+                for q in range(len(nodes))]
+    hi = 1 / cal["beta"] - 1 if r_high is None else r_high
+    tr = gb.multisection(gb._with_many(many), r_low, hi, max_steps=steps, levels=levels, tol=k_tol)
+    r = tr.r
+    R = egm_solve(guess.T, a, s, P, r, wage(r), cal["beta"], cal["sigma"], cal["amin"], tol,
+                  max_iter)
+    lam, K, _, _ = dist_stationary(a, P, policy_k=R["policy_k"], tol=gb.HIST_TOL,
+                                   max_iter=gb.HIST_MAX_ITER, vfi_layout=False)
+    return dict(r=r, w=wage(r), K=K, policy_c=np.ascontiguousarray(R["policy_c"].T),
+                lam=np.ascontiguousarray(lam.T), cal=cal)
+
+
+def aiyagari_transition(ss, Z, T=None, damp=0.5, tol=1e-6, max_iter=200, backend=None):
+    """The transitions after C unexpected TFP paths Z [C][T] from the steady state ss
+    (steady_state's dict), by a lockstep damped fixed point on the capital paths.  Every path
+    starts at K ≡ K_ss; a round prices the paths still running (prices_from_K; the terminal rate
+    is r_ss), runs them through ONE transition_batch call — backend(r, w, pc_T, lam0, a_grid, s,
+    P, beta, sigma, amin) -> (K_supply, status, fail_t), the GPU's by default — and updates
+    K ← (1 − damp)·K + damp·K_supply with K_0 held at K_ss.  A path stops when
+    max_t |K_supply − K| < tol (measured before the update), when its backend status is not 0,
+    or after max_iter rounds.  A path's arithmetic does not depend on the others in its batch.
+    Returns dict(K [C][T+1], r [C][T+1], w [C][T], rounds [C], status [C], resid [C])."""
+    Z = np.atleast_2d(np.asarray(Z, np.float64))
+    if T is None:
+        T = Z.shape[1]
+    if Z.shape[1] != T or T < 1:
+        raise ValueError("Z must be [C][T] with T >= 1")
+    run = transition_batch if backend is None else backend
+    cal = ss["cal"]
+    n_c = Z.shape[0]
+    K = np.full((n_c, T + 1), float(ss["K"]))
+    rounds, status = np.zeros(n_c, np.int64), np.zeros(n_c, np.int32)
+    resid = np.full(n_c, np.nan)
+    live = np.arange(n_c)
+
+    def price(Kc, Zc):
+        r, w = prices_from_K(Kc[:, :T], Zc, ss)
+        return np.concatenate([r, np.full((len(Kc), 1), float(ss["r"]))], axis=1), w
+    for _ in range(max_iter):
+        if live.size == 0:
+            break
+        r, w = price(K[live], Z[live])
+        Ks, st, _ = run(r, w, ss["policy_c"], ss["lam"], cal["a_grid"], cal["s"], cal["P"],
+                        cal["beta"], cal["sigma"], cal["amin"])
+        rounds[live] += 1
+        status[live] = st
+        ok = st == 0
+        gap = np.full(live.size, np.nan)
+        gap[ok] = np.max(np.abs(Ks[ok] - K[live[ok]]), axis=1)
+        resid[live] = gap
+        upd = live[ok]
+        new = (1 - damp) * K[upd] + damp * Ks[ok]
+        new[:, 0] = float(ss["K"])
+        done = gap[ok] < tol
+        K[upd[~done]] = new[~done]
+        live = upd[~done]
+    r, w = price(K, Z)
+    return dict(K=K, r=r, w=w, rounds=rounds, status=status, resid=resid)

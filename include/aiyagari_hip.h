@@ -612,6 +612,62 @@ int aiy_ws_set_dist_batch(aiy_ws* ws, int min_candidates);
  * many candidates it solved one by one (both nullable) */
 int aiy_ws_dist_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_solves);
 
+/* ---- Transition paths (perfect foresight, MIT shocks; new — the scripts are stationary).
+ * C price paths of T periods per call, ONE workgroup per path and pass, no launch between
+ * periods.  Arrays are [N][Na] rows per (path, period).  A shape whose arrays do not fit one CU's
+ * LDS is refused with AIY_BAD_ARG (no per-step fallback):
+ *   backward: N <= 16, Na <= 1024, (2N+1)·Na doubles + 2.4 KB within 160 KiB;
+ *   forward:  N <= 16, 8·N·Na·3 + 4·N·(Na+1) + 8·Na + 2.2 KB within 160 KiB.
+ * The two-rate EGM step of period t (pc_next = the consumption policy of period t+1):
+ *   RHS(j,a) = sum_m ((beta(1+r[t+1])) P(j,m)) u'(pc_next(m,a)),  c~ = RHS^(-1/sigma),
+ *   a^(j,a) = ((c~ + a_grid(a)) - w[t] s_j) / (1 + r[t]),
+ *   g = interp1(a^_j, a_grid, a_grid(a), linear, extrap), g < amin -> amin,
+ *   pk_t = g,  pc_t = ((1 + r[t]) a_grid(a) + w[t] s_j) - g
+ * — aiy_egm_step's operations with r split in two: on r[t+1] == r[t] it equals that step bit for
+ * bit.  (The labour step, A5, has no transition entry.)
+ *
+ * Backward pass on device: r host [C][T+1] (r[c][T]: the terminal rate of period T-1's Euler
+ * equation), w host [C][T]; pc_T device [C][N][Na], or one [N][Na] for all paths (pc_T_shared);
+ * policy_k, policy_c (nullable): device [C][T][N][Na]; status, fail_t: host [C].  Exactly T steps
+ * from t = T-1 down.  status 1: the endogenous grid of period fail_t was not increasing (NaN
+ * included) — that path stops there (periods above fail_t are complete, the others undefined);
+ * the other paths are unaffected and the call returns AIY_OK.  Refused on the host before any
+ * launch: C < 1, T < 1, a non-finite r or w, 1 + r <= 0.  Synchronises once. */
+int aiy_egm_backward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r, const double* w,
+                               const double* pc_T, int pc_T_shared, const double* a_grid,
+                               const double* s, const double* P, double beta, double sigma,
+                               double amin, double* policy_k, double* policy_c, int32_t* status,
+                               int32_t* fail_t, void* stream);
+/* Forward pass on device: from lambda0 (device [C][N][Na], or one [N][Na]: lambda0_shared), period
+ * t = 0 .. T-1: the lottery plan of policy_k[c][t] (aiy_dist_update_dev's), K[c][t] = sum
+ * lambda_t a (aiy_dist_stationary_dev's k_supply sum), one push.  K: device [C][T+1] (K[c][T] of
+ * the last lambda); lambda_T (nullable): device [C][N][Na]; status, fail_t: host [C].  status 2:
+ * the keys of policy_k[c][fail_t] are not monotone — that path stops there (K up to fail_t is
+ * written, the rest NaN, lambda_T = lambda at fail_t).  Synchronises once. */
+int aiy_dist_forward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* policy_k,
+                               const double* lambda0, int lambda0_shared, const double* a_grid,
+                               const double* P, double* K, double* lambda_T, int32_t* status,
+                               int32_t* fail_t, void* stream);
+/* The same two passes on host arrays (P column-major N x N, as aiy_egm_step).  Also refused
+ * before any launch: an a_grid that is not strictly increasing. */
+int aiy_egm_backward_batch(int64_t C, int64_t T, const double* r, const double* w,
+                           const double* pc_T, int pc_T_shared, const double* a_grid,
+                           const double* s, const double* P, int64_t N, int64_t Na, double beta,
+                           double sigma, double amin, double* policy_k, double* policy_c,
+                           int32_t* status, int32_t* fail_t);
+int aiy_dist_forward_batch(int64_t C, int64_t T, const double* policy_k, const double* lambda0,
+                           int lambda0_shared, const double* a_grid, const double* P, int64_t N,
+                           int64_t Na, double* K, double* lambda_T, int32_t* status,
+                           int32_t* fail_t);
+/* Both passes on one stream: the period policies stay on the device and the host reads K
+ * [C][T+1], status and fail_t [C] only.  A path the backward pass stopped (status 1) has K all
+ * NaN; status 2 as aiy_dist_forward_batch_dev. */
+int aiy_transition_batch(int64_t C, int64_t T, const double* r, const double* w,
+                         const double* pc_T, int pc_T_shared, const double* lambda0,
+                         int lambda0_shared, const double* a_grid, const double* s,
+                         const double* P, int64_t N, int64_t Na, double beta, double sigma,
+                         double amin, double* K, int32_t* status, int32_t* fail_t);
+
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
  * arrays (the layout of Krusell_Smith_VFI.m's `value`).  Each call writes only the shard's
