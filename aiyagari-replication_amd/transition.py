@@ -7,6 +7,7 @@ C paths run per call, one workgroup per path and pass (include/aiyagari_hip.h, "
 paths").  Arrays are [N][Na] rows per (path, period), C-contiguous: policy_k [C][T][N][Na]."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
@@ -213,6 +214,172 @@ def aiyagari_transition(ss, Z, T=None, damp=0.5, tol=1e-6, max_iter=200, backend
         new[:, 0] = float(ss["K"])
         done = gap[ok] < tol
         K[upd[~done]] = new[~done]
+        live = upd[~done]
+    r, w = price(K, Z)
+    return dict(K=K, r=r, w=w, rounds=rounds, status=status, resid=resid)
+
+
+# ------------------------------------------------------------- sequence-space Jacobian
+def expectation_batch(policy_k, y0, a_grid, P, T):
+    """aiy_dist_expect_batch: the expectation vectors of C constant policies, policy_k [C][N][Na]
+    (or one [N][Na]), y0 [N][Na] (shared) or [C][N][Na].  Returns E [C][T][N][Na]: E[c][t]·λ₀ is
+    the mean of y0 t periods after λ₀ under policy_k[c]."""
+    pk = _f(policy_k)
+    if pk.ndim == 2:
+        pk = pk[None]
+    if pk.ndim != 3:
+        raise ValueError("policy_k must be [C][N][Na]")
+    n_c, N, Na = pk.shape
+    a, P = _f(a_grid), np.asfortranarray(P, dtype=np.float64)
+    y, shared = _start(y0, n_c, N, Na, "y0")
+    E = np.empty((n_c, max(int(T), 0), N, Na))
+    check(lib().aiy_dist_expect_batch(i64(n_c), i64(T), ptr(pk), ptr(y), ip(shared), ptr(a),
+                                      ptr(P), i64(N), i64(Na), ptr(E)))
+    return E
+
+
+def expectation_batch_dev(ws, policy_k, y0, a_grid, P, E, stream=None):
+    """aiy_dist_expect_batch_dev (torch tensors): policy_k [C][N][Na], y0 [N][Na] (shared) or
+    [C][N][Na], E [C][T][N][Na] (out); P row-major.  Enqueues only."""
+    from ._capi import stream_handle
+    check(lib().aiy_dist_expect_batch_dev(ws.handle, i64(E.shape[0]), i64(E.shape[1]),
+                                          ptr(policy_k), ptr(y0), ip(1 if y0.dim() == 2 else 0),
+                                          ptr(a_grid), ptr(P), ptr(E), stream_handle(stream)))
+
+
+def fake_news(E, lam1, h):
+    """aiy_ssj_fake_news: E [T][...n], lam1 [n_in+1][T][...n] (block 0 the base path's one-step
+    distributions).  Returns (F, J), each [n_in][T][T]: F[x][t][s] = E[t]·(lam1[x+1][T−1−s] −
+    lam1[0][T−1−s])/h and J its sum down each diagonal."""
+    E, L = _f(E), _f(lam1)
+    T = E.shape[0]
+    if E.ndim < 2 or L.ndim != E.ndim + 1 or L.shape[1:] != E.shape or L.shape[0] < 2:
+        raise ValueError("E must be [T][...] and lam1 [n_in+1][T][...] over the same states")
+    n_in, n = L.shape[0] - 1, E.size // max(T, 1)
+    F, J = np.empty((n_in, T, T)), np.empty((n_in, T, T))
+    check(lib().aiy_ssj_fake_news(i64(T), i64(n_in), i64(n), ptr(E), ptr(L), d(h), ptr(F), ptr(J)))
+    return F, J
+
+
+def fake_news_dev(E, lam1, h, F, J, stream=None):
+    """aiy_ssj_fake_news_dev (torch tensors): E [T][n], lam1 [n_in+1][T][n], F, J [n_in][T][T]
+    (out).  Enqueues only."""
+    from ._capi import stream_handle
+    check(lib().aiy_ssj_fake_news_dev(i64(E.shape[0]), i64(lam1.shape[0] - 1), i64(E.shape[1]),
+                                      ptr(E), ptr(lam1), d(h), ptr(F), ptr(J),
+                                      stream_handle(stream)))
+
+
+def jacobian(ss, T, h=1e-4, stage_ms=None):
+    """aiy_ssj_jacobian: the sequence-space Jacobians of the capital path around the steady state
+    ss (steady_state's dict) by the fake-news algorithm — one backward pass of three price paths,
+    one push of each of their 3T period policies, T − 1 transposed pushes and one T × T × N·Na
+    contraction.  Returns dict(J_r, J_w, F_r, F_w [T][T], E [T][N][Na], status (backward,
+    forward)); J_x[t][s] = ∂K_{t+1}/∂x_s.  A non-zero status: J_r and J_w are NaN.
+    stage_ms: an optional float64 [4] array that receives the four stages' device times."""
+    cal = ss["cal"]
+    a, s, P = _f(cal["a_grid"]), _f(cal["s"]), np.asfortranarray(cal["P"], dtype=np.float64)
+    N, Na = s.size, a.size
+    pc, lam = _f(ss["policy_c"]), _f(ss["lam"])
+    if pc.shape != (N, Na) or lam.shape != (N, Na):
+        raise ValueError("ss['policy_c'] and ss['lam'] must be [N][Na]")
+    Tn = max(int(T), 0)
+    J_r, J_w, F_r, F_w = (np.empty((Tn, Tn)) for _ in range(4))
+    E = np.empty((Tn, N, Na))
+    sb, sf = ip(0), ip(0)
+    check(lib().aiy_ssj_jacobian(ptr(pc), ptr(lam), d(ss["r"]), d(ss["w"]), ptr(a), ptr(s), ptr(P),
+                                 i64(N), i64(Na), d(cal["beta"]), d(cal["sigma"]), d(cal["amin"]),
+                                 i64(T), d(h), ptr(J_r), ptr(J_w), ptr(F_r), ptr(F_w), ptr(E),
+                                 ctypes.byref(sb), ctypes.byref(sf), ptr(stage_ms)))
+    return dict(J_r=J_r, J_w=J_w, F_r=F_r, F_w=F_w, E=E, status=(sb.value, sf.value))
+
+
+def _price_slopes(ss):
+    """∂r/∂K, ∂w/∂K, ∂r/∂Z, ∂w/∂Z of prices_from_K at the steady state."""
+    alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]
+    r_K = (ss["r"] + delta) * (alpha - 1) / ss["K"]
+    w_K = ss["w"] * alpha / ss["K"]
+    return r_K, w_K, ss["r"] + delta, ss["w"]
+
+
+def _newton_matrix(ss, jac):
+    """M − I, M = ∂K_supply[1:]/∂K[1:]: K_j moves r_j and w_j, j = 1 … T−1 (K_T moves no price
+    inside the horizon: M's last column is zero)."""
+    J_r, J_w = _f(jac["J_r"]), _f(jac["J_w"])
+    r_K, w_K, _, _ = _price_slopes(ss)
+    T = J_r.shape[0]
+    M = np.zeros((T, T))
+    M[:, :T - 1] = J_r[:, 1:] * r_K + J_w[:, 1:] * w_K
+    return M - np.eye(T)
+
+
+def impulse_response(ss, jac, dZ):
+    """The linear response dK [C][T+1] (dK_0 = 0) of the capital path to the TFP paths 1 + dZ,
+    dZ [C][T]: (I − M)·dK[1:] = J_r·(∂r/∂Z·dZ) + J_w·(∂w/∂Z·dZ) with M of
+    aiyagari_transition_newton and the slopes of prices_from_K at the steady state.  Each path
+    is its own solve."""
+    dZ = np.atleast_2d(np.asarray(dZ, np.float64))
+    A = -_newton_matrix(ss, jac)
+    _, _, r_Z, w_Z = _price_slopes(ss)
+    J_r, J_w = _f(jac["J_r"]), _f(jac["J_w"])
+    if dZ.shape[1] != J_r.shape[0]:
+        raise ValueError("dZ must be [C][T] with the Jacobian's T")
+    out = np.zeros((dZ.shape[0], dZ.shape[1] + 1))
+    for c in range(dZ.shape[0]):
+        out[c, 1:] = np.linalg.solve(A, J_r @ (r_Z * dZ[c]) + J_w @ (w_Z * dZ[c]))
+    return out
+
+
+def aiyagari_transition_newton(ss, Z, T=None, jac=None, tol=1e-6, max_iter=50, backend=None):
+    """aiyagari_transition with a Newton update from the steady state's sequence-space Jacobian:
+    the same arguments, lockstep rounds, stopping rule (max_t |K_supply − K| < tol, measured
+    before the update), statuses and return dict; the update is
+        K[1:] ← K[1:] − (M − I)⁻¹·(K_supply − K)[1:],   K_0 held at K_ss,
+    M[:, j−1] = J_r[:, j]·r_K + J_w[:, j]·w_K (j = 1 … T−1, last column zero), r_K = (r_ss + δ)
+    (α − 1)/K_ss, w_K = w_ss·α/K_ss.  The same (M − I) serves every round and path; a path's update
+    is its own single-right-hand-side solve, so its arithmetic does not depend on its batch.
+    jac: jacobian(ss, T)'s dict (computed once when None)."""
+    Z = np.atleast_2d(np.asarray(Z, np.float64))
+    if T is None:
+        T = Z.shape[1]
+    if Z.shape[1] != T or T < 1:
+        raise ValueError("Z must be [C][T] with T >= 1")
+    run = transition_batch if backend is None else backend
+    if jac is None:
+        jac = jacobian(ss, T)
+    if np.shape(jac["J_r"]) != (T, T) or np.shape(jac["J_w"]) != (T, T):
+        raise ValueError("jac must hold J_r and J_w [T][T]")
+    A = _newton_matrix(ss, jac)
+    if not np.isfinite(A).all():
+        raise ValueError(f"the Jacobian is not finite (jacobian()'s status: {jac.get('status')})")
+    cal = ss["cal"]
+    n_c = Z.shape[0]
+    K = np.full((n_c, T + 1), float(ss["K"]))
+    rounds, status = np.zeros(n_c, np.int64), np.zeros(n_c, np.int32)
+    resid = np.full(n_c, np.nan)
+    live = np.arange(n_c)
+
+    def price(Kc, Zc):
+        r, w = prices_from_K(Kc[:, :T], Zc, ss)
+        return np.concatenate([r, np.full((len(Kc), 1), float(ss["r"]))], axis=1), w
+    for _ in range(max_iter):
+        if live.size == 0:
+            break
+        r, w = price(K[live], Z[live])
+        Ks, st, _ = run(r, w, ss["policy_c"], ss["lam"], cal["a_grid"], cal["s"], cal["P"],
+                        cal["beta"], cal["sigma"], cal["amin"])
+        rounds[live] += 1
+        status[live] = st
+        ok = st == 0
+        gap = np.full(live.size, np.nan)
+        gap[ok] = np.max(np.abs(Ks[ok] - K[live[ok]]), axis=1)
+        resid[live] = gap
+        upd = live[ok]
+        done = gap[ok] < tol
+        Kok = Ks[ok]
+        for q in np.flatnonzero(~done):
+            c = upd[q]
+            K[c, 1:] = K[c, 1:] - np.linalg.solve(A, (Kok[q] - K[c])[1:])
         live = upd[~done]
     r, w = price(K, Z)
     return dict(K=K, r=r, w=w, rounds=rounds, status=status, resid=resid)

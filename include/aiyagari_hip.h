@@ -667,6 +667,54 @@ int aiy_transition_batch(int64_t C, int64_t T, const double* r, const double* w,
                          int lambda0_shared, const double* a_grid, const double* s,
                          const double* P, int64_t N, int64_t Na, double beta, double sigma,
                          double amin, double* K, int32_t* status, int32_t* fail_t);
+/* Sequence-space Jacobian of the capital path (fake-news algorithm; n = N·Na).
+ *
+ * Expectation vectors of C policies: with dist_update's lottery plan of policy_k[c] (x = the
+ * policy clamped to the grid, lo its bracket, wr = (x - a(lo)) / (a(lo+1) - a(lo)), wl = 1 - wr),
+ * E_0 = y0 and, t = 0 .. T-2,
+ *   G_t(i,k') = sum_m P(i,m) E_t(m,k')  (m ascending),
+ *   E_{t+1}(i,k) = wl(i,k) G_t(i,lo(i,k)) + (1 - wl(i,k)) G_t(i,lo(i,k)+1)
+ * — the transpose of the forward pass's push: E_t·lambda_0 = y0·lambda_t under the constant
+ * policy.  No fused multiply-adds.  policy_k: [C][N][Na]; y0: [C][N][Na], or one [N][Na] for all
+ * (y0_shared); E: [C][T][N][Na].  ONE workgroup per c, exactly T-1 steps.  Fit rule (else
+ * AIY_BAD_ARG, no per-step fallback): N <= 16, 28·N·Na + 2 KB within 160 KiB.  A NaN in
+ * policy_k[c] stays inside E[c].  The device entry only enqueues on `stream`. */
+int aiy_dist_expect_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* policy_k,
+                              const double* y0, int y0_shared, const double* a_grid,
+                              const double* P, double* E, void* stream);
+/* host arrays; P column-major N x N; also refused: an a_grid that is not strictly increasing */
+int aiy_dist_expect_batch(int64_t C, int64_t T, const double* policy_k, const double* y0,
+                          int y0_shared, const double* a_grid, const double* P, int64_t N,
+                          int64_t Na, double* E);
+/* Fake-news matrices and Jacobians of n_in inputs.  E: [T][n]; lambda1: [n_in + 1][T][n], block 0
+ * the base path's one-step distributions, block x + 1 those of input x, period T-1-s holding the
+ * response to news s periods ahead.  With D_x[s] = (lambda1[x+1][T-1-s] - lambda1[0][T-1-s]) / h
+ * (elementwise; never stored),
+ *   F[x][t][s] = sum_k E[t][k] D_x[s][k]   (fp64 matrix cores, k ascending in steps of 4),
+ *   J[x][t][s] = F[x][t][s] + J[x][t-1][s-1] for t, s >= 1, = F[x][t][s] otherwise.
+ * F, J: [n_in][T][T].  An entry's bits depend on its own row of E and of D only — not on n_in,
+ * the other entries or the run (no atomics).  Refused: T outside [1, 32768], n_in outside
+ * [1, 65535], n < 1, h <= 0 or not finite.  The device entry only enqueues on `stream`. */
+int aiy_ssj_fake_news_dev(int64_t T, int64_t n_in, int64_t n, const double* E,
+                          const double* lambda1, double h, double* F, double* J, void* stream);
+int aiy_ssj_fake_news(int64_t T, int64_t n_in, int64_t n, const double* E, const double* lambda1,
+                      double h, double* F, double* J);
+/* The Jacobians of K_{t+1} in r_s and w_s around a steady state (host arrays; policy_c, lambda:
+ * [N][Na]; P column-major), everything between the inputs and J staying on the device:
+ *   1. aiy_egm_backward_batch's pass of 3 paths from policy_c: r = r_ss, w = w_ss; r[T-1] + h;
+ *      w[T-1] + h;
+ *   2. aiy_dist_forward_batch's pass of the 3T period policies, one push each from lambda;
+ *   3. the expectation vectors of the base path's period-0 policy, y0 = a_grid in every row;
+ *   4. the fake-news matrices, and 5. the Jacobians, of the two inputs.
+ * J_r, J_w: [T][T], J[t][s] = dK_{t+1}/dx_s; F_r, F_w [T][T] and E [T][N][Na] are nullable.
+ * *backward_status / *forward_status: the OR of the passes' per-path status words; if either is
+ * not 0 the Jacobians are NaN (the call still returns AIY_OK).  stage_ms (nullable): the device
+ * time of stages 1, 2, 3 and 4-5 in ms, from events recorded as they are dispatched. */
+int aiy_ssj_jacobian(const double* policy_c, const double* lambda, double r_ss, double w_ss,
+                     const double* a_grid, const double* s, const double* P, int64_t N,
+                     int64_t Na, double beta, double sigma, double amin, int64_t T, double h,
+                     double* J_r, double* J_w, double* F_r, double* F_w, double* E,
+                     int32_t* backward_status, int32_t* forward_status, double* stage_ms);
 
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
