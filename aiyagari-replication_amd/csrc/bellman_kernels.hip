@@ -1443,36 +1443,53 @@ __device__ __forceinline__ void bell_tree_item(const BellArgs& A0, int ntile, in
             }
             if constexpr (GF) {
                 // Trips: every lane takes the lowest block left in its group's mask (ascending,
-                // as the union walk visited them); a group that has run out reads the wave's
-                // highest passing block, which is staged.  The walk ends when no group has a
-                // block left: as many trips as the busiest group has blocks.
+                // as the union walk visited them).  The walk ends when no group has a block
+                // left: as many trips as the busiest group has blocks.
+                // In 32-bit windows: the superblock's passing blocks are
+                // taken in windows of 32 from the lowest one left — one window whenever the
+                // union spans fewer than 32 blocks, as it does in every superblock of the
+                // headline — and inside a window every group's mask is one word counted from
+                // the window's first block lb: the trip's per-lane bit walk is one ffbl, one
+                // min, a 32-bit clear and a 32-bit compare, and lb sits in the scalar bases of
+                // k0 and of the LDS address.  Per lane the blocks are still its group's,
+                // ascending; a group that has run out reads the window's highest passing
+                // block, which is staged.
                 pm = 0;
                 const int hb = 63 - __builtin_clzll(pass);
                 const bool ncl = FAST && sbase + (hb << 3) + 8 <= kfmin;
-                auto next = [&](int& k0) __attribute__((always_inline)) {
-                    const unsigned lo = (unsigned)gm, hi = (unsigned)(gm >> 32);
-                    const unsigned tl = lo ? (unsigned)__builtin_ctz(lo) : ~0u;
-                    const unsigned th = hi ? ((unsigned)__builtin_ctz(hi) | 32u) : ~0u;
-                    const int b = (int)min(min(tl, th), (unsigned)hb);
-                    gm &= gm - 1;
-                    k0 = sbase + (b << 3);
-                    return b;
-                };
-                int kA, kB;
-                bool actA = gm != 0, actB;
-                load_tk(next(kA), tkA);
-                for (;;) {
-                    actB = gm != 0;
-                    const bool moreB = __any(actB);
-                    if (moreB) load_tk(next(kB), tkB);
-                    fine(sbase, kA, 0, tkA, actA, ncl);
-                    if (!moreB) break;
-                    actA = gm != 0;
-                    const bool moreA = __any(actA);
-                    if (moreA) load_tk(next(kA), tkA);
-                    fine(sbase, kB, 0, tkB, actB, ncl);
-                    if (!moreA) break;
-                }
+                unsigned long long pw = pass;
+                do {
+                    const int lb = __builtin_ctzll(pw);
+                    const unsigned wu = (unsigned)(pw >> lb);  // the union's bits in the window
+                    const unsigned hw = 31u - (unsigned)__builtin_clz(wu);
+                    const int kb0 = sbase + (lb << 3);
+                    const double2* sc0 = &s_cand[lw][lb << 3];
+                    unsigned g = (unsigned)(gm >> lb);
+                    pw = lb >= 32 ? 0ull : pw & (~0ull << (lb + 32));
+                    // the lane's next block: its first candidate k0, its eight candidates
+                    auto next = [&](int& k0, double2 (&tk)[8]) __attribute__((always_inline)) {
+                        const int b = (int)min(g ? (unsigned)__builtin_ctz(g) : ~0u, hw);
+                        g &= g - 1;
+                        k0 = kb0 + (b << 3);
+#pragma unroll
+                        for (int kk = 0; kk < 8; ++kk) tk[kk] = sc0[(b << 3) + kk];
+                    };
+                    int kA, kB;
+                    bool actA = g != 0, actB;
+                    next(kA, tkA);
+                    for (;;) {
+                        actB = g != 0;
+                        const bool moreB = __any(actB);
+                        if (moreB) next(kB, tkB);
+                        fine(sbase, kA, 0, tkA, actA, ncl);
+                        if (!moreB) break;
+                        actA = g != 0;
+                        const bool moreA = __any(actA);
+                        if (moreA) next(kA, tkA);
+                        fine(sbase, kB, 0, tkB, actB, ncl);
+                        if (!moreA) break;
+                    }
+                } while (pw);
             }
             if (pm) load_tk(__builtin_ctzll(pm), tkA);
             while (pm) {

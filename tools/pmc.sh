@@ -19,6 +19,7 @@ for ps in ${PASSES:-sq sq2 grbm fetch write}; do
   case $ps in
     sq)    pass sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU ;;
     sq2)   pass sq2 SQ_WAVES SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_BRANCH SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA ;;
+    lds)   pass lds SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE ;;
     grbm)  pass grbm GRBM_GUI_ACTIVE GRBM_COUNT ;;
     fetch) pass fetch FETCH_SIZE ;;
     write) pass write WRITE_SIZE ;;
