@@ -6,10 +6,11 @@
 // The policy is fixed across the fixed-point iteration, so its plan (keys, lottery weights,
 // run offsets, the monotonicity flag) is built ONCE per call and read back once; every push is
 // then one launch (dist_push_kernel).  The iteration runs in speculative batches as the VFI
-// and EGM solves do: m pushes are enqueued per batch — push g reads ring slot (g−1) mod R
-// and writes slot g mod R, its max|Δλ| lands in its own slot set — and the host reads one
-// batch's slot sets while the next batch runs, to find the first push with max|Δλ| < tol.  Pushes are deterministic, so the iteration count,
-// the returned λ and dist are exactly the one-read-per-push loop's.
+// and EGM solves do (spec_loop.hpp): m pushes are enqueued per batch — push g reads ring slot
+// (g−1) mod R and writes slot g mod R, its max|Δλ| lands in its own slot set — and the host reads
+// one batch's slot sets while the next batch runs, to find the first push with max|Δλ| < tol.
+// Pushes are deterministic, so the iteration count, the returned λ and dist are exactly the
+// one-read-per-push loop's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "aiy_common.hpp"
 #include "dist.hpp"
 #include "host_ctx.hpp"
+#include "spec_loop.hpp"
 #include "ws.hpp"
 
 namespace aiy {
@@ -116,73 +118,40 @@ int dist_stationary_dev(aiy_ws* ws, const double* lam0, const int* idx, const do
     auto sset = [&](int64_t g) { return dr.slots + (size_t)(g % R) * SW; };
     AIY_HIP(hipMemcpyAsync(slot(0), lam0, nb, hipMemcpyDeviceToDevice, st));
     AIY_HIP(hipMemsetAsync(sset(1), 0, SW * sizeof(unsigned long long), st));
-    struct Batch {
-        int64_t s0, m;  // pushes s0 + 1 .. s0 + m
-        int hb;
+    auto push = [&](int64_t g) -> int {
+        DistArgs A = A0;
+        A.lam = slot(g - 1);
+        A.out = slot(g);
+        A.diff = sset(g);
+        // push g's set was zeroed by push g−1 (one-launch push) or is zeroed here
+        if (two_launch) AIY_HIP(hipMemsetAsync(sset(g), 0, SW * sizeof(unsigned long long), st));
+        else A.diff_clear = sset(g + 1);
+        AIY_TRY(ws_dispatch_arm(ws));  // the push's own duration (one-launch push)
+        const int rc = launch_dist_push(A, fb, st);
+        ws_dispatch_commit(ws);
+        return rc;
     };
-    Batch q[2];
-    int nq = 0, hb_next = 0;
-    int64_t enq = 0, stop = 0;
-    double d_prev = NAN, d_last = NAN, d_stop = NAN;
-    auto enqueue = [&]() -> int {
-        int64_t m = M;
-        if (d_last == d_last && d_prev == d_prev && d_last < d_prev && d_last > 0 && tol > 0) {
-            const double need = std::ceil(std::log(tol / d_last) / std::log(d_last / d_prev));
-            int64_t ahead = 0;  // pushes in flight, not yet read
-            for (int b = 0; b < nq; ++b) ahead += q[b].m;
-            if (need >= 1 && need - (double)ahead < (double)m)
-                m = (int64_t)std::max(1.0, need - (double)ahead);
-        }
-        m = std::min<int64_t>(std::max<int64_t>(m, 1), max_iter - enq);
-        for (int64_t t = 0; t < m; ++t) {
-            const int64_t g = enq + 1 + t;
-            DistArgs A = A0;
-            A.lam = slot(g - 1);
-            A.out = slot(g);
-            A.diff = sset(g);
-            // push g's set was zeroed by push g−1 (one-launch push) or is zeroed here
-            if (two_launch) AIY_HIP(hipMemsetAsync(sset(g), 0, SW * sizeof(unsigned long long), st));
-            else A.diff_clear = sset(g + 1);
-            AIY_TRY(ws_dispatch_arm(ws));  // the push's own duration (one-launch push)
-            const int rc = launch_dist_push(A, fb, st);
-            ws_dispatch_commit(ws);
-            AIY_TRY(rc);
-        }
-        unsigned long long* h = dr.hslots + (size_t)hb_next * R * SW;
-        AIY_HIP(hipMemcpyAsync(h, dr.slots, SB, hipMemcpyDeviceToHost, st));
-        AIY_HIP(hipEventRecord(dr.ev[hb_next], st));
-        q[nq++] = Batch{enq, m, hb_next};
-        hb_next ^= 1;
-        enq += m;
+    auto flush = [&](int hb) -> int {
+        AIY_HIP(hipMemcpyAsync(dr.hslots + (size_t)hb * R * SW, dr.slots, SB,
+                               hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipEventRecord(dr.ev[hb], st));
         return AIY_OK;
     };
-    AIY_TRY(enqueue());
-    while (nq > 0) {
-        if (nq < 2 && enq < max_iter) AIY_TRY(enqueue());  // keep the device busy while reading
-        const Batch b = q[0];
-        AIY_TRY(wait_event(dr.ev[b.hb]));
-        const unsigned long long* hs = dr.hslots + (size_t)b.hb * R * SW;
-        for (int64_t t = 0; t < b.m; ++t) {
-            const double d = fold_slots_host(hs + (size_t)((b.s0 + 1 + t) % R) * SW);
-            d_prev = d_last;
-            d_last = d;
-            d_stop = d;
-            if (d < tol) {
-                stop = b.s0 + 1 + t;
-                break;
-            }
-        }
-        q[0] = q[1];
-        --nq;
-        if (stop) break;
-    }
-    const int64_t g = stop ? stop : enq;
+    auto wait = [&](int hb) { return wait_event(dr.ev[hb]); };
+    auto read = [&](int64_t g, int hb, double* d) -> int {
+        *d = fold_slots_host(dr.hslots + ((size_t)hb * R + (size_t)(g % R)) * SW);
+        return AIY_OK;
+    };
+    SpecResult S;
+    AIY_TRY(spec_loop(M, max_iter, tol, &S, push, flush, wait, read,
+                      [tol](double d) { return d < tol; }));
+    const int64_t g = S.g;
     AIY_HIP(hipMemcpyAsync(lam_out, slot(g), nb, hipMemcpyDeviceToDevice, st));
     if (k_dev)
         AIY_TRY(launch_dist_capital(lam_out, a, (int)ws->N, (int)ws->Na, ws->d_part, k_dev, st));
     AIY_HIP(hipStreamSynchronize(st));  // (a speculative batch may still be running)
     *iters = g;
-    *dist = d_stop;
+    *dist = S.d;
     return AIY_OK;
 }
 

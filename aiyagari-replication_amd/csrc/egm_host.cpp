@@ -11,6 +11,7 @@
 #include "aiy_common.hpp"
 #include "egm.hpp"
 #include "host_ctx.hpp"
+#include "spec_loop.hpp"
 #include "ws.hpp"
 
 namespace aiy {
@@ -103,12 +104,12 @@ static int read_egm(aiy_ws* ws, hipStream_t st, double* d) {
     return AIY_OK;
 }
 
-// The solve loop (Aiyagari_EGM.m:74-108, labour :67-105) with speculative batches, as the VFI
-// solve (capi.cpp, bell_solve_spec): steps are deterministic, so batches of m steps are
-// enqueued between reads — step g reads ring slot (g−1) mod R and writes slot g mod R, its
-// dist lands in slot set g mod R with its flag word (a chained step zeroes set (g+1) mod R for
-// the next step; the other steps clear their own) — and each batch ends with
-// one D2H copy of the slot sets and an event.  Two batches are in flight: the host reads batch
+// The solve loop (Aiyagari_EGM.m:74-108, labour :67-105) with speculative batches, the loop of
+// the VFI solve (spec_loop.hpp; bell_host.cpp, bell_solve_spec): steps are deterministic, so
+// batches of m steps are enqueued between reads — step g reads ring slot (g−1) mod R and writes
+// slot g mod R, its dist lands in slot set g mod R with its flag word (a chained step zeroes set
+// (g+1) mod R for the next step; the other steps clear their own) — and each batch ends with one
+// D2H copy of the slot sets and an event.  Two batches are in flight: the host reads batch
 // k's dists while batch k+1 runs, so the device never idles at a read; with R = 2M + 1 slots
 // the stopping step's policy_c survives the next batch's writes.  Its policy_k (and policy_l)
 // were overwritten by later speculative steps, so the stopping step is re-run from its input
@@ -161,61 +162,27 @@ static int egm_solve_spec(aiy_ws* ws, const EgmArgs& A0, double* c0, double tol,
         A.flags = (unsigned*)(sset(1) + 2 * kDiffSlots);
         AIY_TRY(launch_egm_rhs(A, st));
     }
-    struct Batch {
-        int64_t s0, m;  // steps s0 + 1 .. s0 + m
-        int hb;         // host half holding its slot sets
-    };
-    Batch q[2];
-    int nq = 0, hb_next = 0;
-    int64_t enq = 0, stop = 0;
-    double d_prev = NAN, d_last = NAN, d_stop = 1.0;
-    auto enqueue = [&]() -> int {
-        int64_t m = M;
-        if (d_last == d_last && d_prev == d_prev && d_last < d_prev && d_last > 0) {
-            // steps the observed geometric decay still needs, counted from the last read
-            const double need = std::ceil(std::log(tol / d_last) / std::log(d_last / d_prev));
-            int64_t ahead = 0;  // steps in flight, not yet read
-            for (int b = 0; b < nq; ++b) ahead += q[b].m;
-            if (need >= 1 && need - (double)ahead < (double)m)
-                m = (int64_t)std::max(1.0, need - (double)ahead);
-        }
-        m = std::min<int64_t>(std::max<int64_t>(m, 1), max_iter - enq);
-        for (int64_t t = 0; t < m; ++t) AIY_TRY(step(enq + 1 + t));
-        unsigned long long* h = eg.hslots + (size_t)hb_next * R * SW;
-        AIY_HIP(hipMemcpyAsync(h, eg.slots, SB, hipMemcpyDeviceToHost, st));
-        AIY_HIP(hipEventRecord(eg.ev[hb_next], st));
-        q[nq++] = Batch{enq, m, hb_next};
-        hb_next ^= 1;
-        enq += m;
+    auto flush = [&](int hb) -> int {
+        AIY_HIP(hipMemcpyAsync(eg.hslots + (size_t)hb * R * SW, eg.slots, SB,
+                               hipMemcpyDeviceToHost, st));
+        AIY_HIP(hipEventRecord(eg.ev[hb], st));
         return AIY_OK;
     };
-    if (max_iter > 0) AIY_TRY(enqueue());
-    while (nq > 0) {
-        if (nq < 2 && enq < max_iter) AIY_TRY(enqueue());  // keep the device busy while reading
-        const Batch b = q[0];
-        AIY_TRY(wait_event(eg.ev[b.hb]));
-        const unsigned long long* hs = eg.hslots + (size_t)b.hb * R * SW;
-        for (int64_t t = 0; t < b.m; ++t) {
-            const unsigned long long* h = hs + (size_t)((b.s0 + 1 + t) % R) * SW;
-            if (egm_nonmonotone(h, (unsigned)h[2 * kDiffSlots])) {
-                AIY_HIP(hipStreamSynchronize(st));
-                return fail_nonmonotone();
-            }
-            const double d = fold_slots_host(h);
-            d_prev = d_last;
-            d_last = d;
-            d_stop = d;
-            if (!(d > tol)) {  // Aiyagari_EGM.m:74 `while dist > tol`
-                stop = b.s0 + 1 + t;
-                break;
-            }
+    auto wait = [&](int hb) { return wait_event(eg.ev[hb]); };
+    auto read = [&](int64_t g, int hb, double* d) -> int {
+        const unsigned long long* h = eg.hslots + ((size_t)hb * R + (size_t)(g % R)) * SW;
+        if (egm_nonmonotone(h, (unsigned)h[2 * kDiffSlots])) {
+            AIY_HIP(hipStreamSynchronize(st));
+            return fail_nonmonotone();
         }
-        q[0] = q[1];
-        --nq;
-        if (stop) break;
-    }
+        *d = fold_slots_host(h);
+        return AIY_OK;
+    };
+    SpecResult S;
+    AIY_TRY(spec_loop(M, max_iter, tol, &S, step, flush, wait, read,
+                      [tol](double d) { return !(d > tol); }));  // Aiyagari_EGM.m:74 `while dist > tol`
     AIY_HIP(hipStreamSynchronize(st));  // (a speculative batch may still be running)
-    const int64_t g = stop ? stop : enq;
+    const int64_t g = S.g, enq = S.enq;
     if (g > 0 && g != enq) {  // policy_k/l of the stopping step (its slots are not read
                               // again): the two-launch step from its input
         EgmArgs A = A0;
@@ -227,7 +194,7 @@ static int egm_solve_spec(aiy_ws* ws, const EgmArgs& A0, double* c0, double tol,
         AIY_TRY(launch_egm_step(A, st));
     }
     *cur_out = g > 0 ? slot(g) : slot(0);
-    *dist = d_stop;
+    *dist = S.any ? S.d : 1.0;  // (no step: the loop's initial dist = 1)
     *iters = g;
     return AIY_OK;
 }

@@ -45,28 +45,36 @@ struct SlotRings {
         return AIY_OK;
     }
 };
+// C candidate rates solved in lockstep (bell_lockstep): the candidates' prices, the sweep each
+// stopped at (0 = running) and the host copies the driver reads
+struct LockstepBlocks {
+    DevBuf<int> stop;       // device [C]
+    DevBuf<double> rw;      // device [2][C]: r then w
+    PinnedBuf<int> hstop;   // [C]
+    PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]: slot sets of the candidates still running
+    int ensure(size_t C) {
+        AIY_TRY(stop.ensure(C));
+        AIY_TRY(rw.ensure(2 * C));
+        AIY_TRY(hstop.ensure(C));
+        return hslots.ensure(C * 2 * kDiffSlots);
+    }
+};
 // batched candidate rates (config 4, aiy_vfi_solve_batch_dev): per-candidate blocks of the
 // tree-screen scratch, sized for C candidates
 struct BatchBlocks {
     int64_t C = 0;
     DevBuf<double> EV, Dt, Dm8, Dm512, best0;
     DevBuf<int> idx0, mom, kf;
-    DevBuf<int> stop;       // device [C]
     DevBuf<u64> slots;      // device [C][2][2*kDiffSlots]
-    DevBuf<double> rw;      // device [2][C]: r then w
-    PinnedBuf<int> hstop;   // [C]
-    PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
+    LockstepBlocks ls;
 };
 // batched labour solve on the small-grid sweep (aiy_labor_vfi_solve_batch_dev): per-candidate
-// feasible prefixes, stop flags, three slot sets each (wide_batch.hpp), sized for C candidates
+// feasible prefixes and three slot sets each (wide_batch.hpp), sized for C candidates
 struct LaborBatchBlocks {
     int64_t C = 0;
     DevBuf<int> kf;         // device [C][Nl][N][Na]
-    DevBuf<int> stop;       // device [C]
     DevBuf<u64> slots;      // device [C][3][2*kDiffSlots]
-    DevBuf<double> rw;      // device [2][C]: r then w
-    PinnedBuf<int> hstop;   // [C]
-    PinnedBuf<u64> hslots;  // [C][2*kDiffSlots]
+    LockstepBlocks ls;
 };
 // transition passes (aiy_egm_backward_batch_dev, aiy_dist_forward_batch_dev): the paths' prices
 // and per-path results on the device and their pinned copies, sized for the largest call seen
