@@ -52,4 +52,25 @@ struct SsjFakeNewsArgs {
 constexpr int kSsjMaxT = 32768;  // T·T entries and the launch grid stay below 2^31 / 65,536
 int launch_ssj_fake_news(const SsjFakeNewsArgs& A, hipStream_t st);
 
+// The labour economy's hours H_t = Σ λ_t·(s_j·pl_t) respond to news at date 0 already (the policy
+// pl_0 itself moves), which the capital path does not.  y [N][Na] = s_j·pl(j,a) is the outcome
+// whose expectation vectors E^h carry the response through the distribution;
+int launch_ssj_hours_outcome(const double* s, const double* pl, int N, int Na, double* y,
+                             hipStream_t st);
+// with G = E^h·D_xᵀ (the fake-news contraction, unchanged) and H1 [n_in+1][T] the hours of the
+// one-step pushes (block 0 the base),
+//   F_H[x][0][s] = (H1[x+1][T−1−s] − H1[0][T−1−s]) / h,   F_H[x][t][s] = G[x][t−1][s]  (t >= 1),
+//   J_H[x][t][s] = F_H[x][t][s] + J_H[x][t−1][s−1]   (ssj_jacobian_kernel, unchanged).
+struct SsjHoursArgs {
+    int T, n_in, n;
+    double h;
+    const double* Eh;    // device [T][n]
+    const double* lam1;  // device [n_in + 1][T][n]
+    const double* H1;    // device [n_in + 1][T]
+    double* G;           // device [n_in][T][T] (scratch)
+    double* F;           // device [n_in][T][T]
+    double* J;           // device [n_in][T][T]
+};
+int launch_ssj_hours_jacobian(const SsjHoursArgs& A, hipStream_t st);
+
 }  // namespace aiy

@@ -1,6 +1,7 @@
 // Sequence-space Jacobian entry points: the expectation vectors (aiy_dist_expect_batch[_dev]), the
 // fake-news contraction (aiy_ssj_fake_news[_dev]) and the whole Jacobian of the capital path in
-// r and w on one stream (aiy_ssj_jacobian: the period policies, Λ1, E and F stay on the device).
+// r and w on one stream (aiy_ssj_jacobian: the period policies, Λ1, E and F stay on the device),
+// and the same of the labour economy's capital and hours paths (aiy_ssj_jacobian_labor).
 // Arrays are [N][Na] rows per block; P is column-major in the host tier (staged as rows),
 // row-major in the device tier.  Everything a host entry can refuse it refuses before it asks
 // for a device.
@@ -219,6 +220,135 @@ int aiy_ssj_jacobian(const double* policy_c, const double* lambda, double r_ss, 
     if (sb | sf) {  // a pass stopped: nothing downstream of it is a derivative
         const double nan = std::numeric_limits<double>::quiet_NaN();
         for (size_t q = 0; q < tt; ++q) J_r[q] = J_w[q] = nan;
+    }
+    if (stage_ms)
+        for (int q = 0; q < 4; ++q) {
+            float ms = 0;
+            AIY_HIP(hipEventElapsedTime(&ms, ev[q], ev[q + 1]));
+            stage_ms[q] = ms;
+        }
+    return AIY_OK;
+}
+
+int aiy_ssj_jacobian_labor(const double* policy_c, const double* lambda, double r_ss,
+                           double w_ss, const double* a_grid, const double* s, const double* P,
+                           int64_t N, int64_t Na, double beta, double sigma, double phi,
+                           double theta, double amin, int64_t T, double h, double* J_Kr,
+                           double* J_Kw, double* J_Hr, double* J_Hw, double* F_Kr, double* F_Kw,
+                           double* F_Hr, double* F_Hw, double* E_a, double* E_h,
+                           int32_t* backward_status, int32_t* forward_status, double* stage_ms) {
+    if (!policy_c || !lambda || !s || !P || !J_Kr || !J_Kw || !J_Hr || !J_Hw ||
+        !backward_status || !forward_status)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need N >= 1 and Na >= 2");
+    if (!labor_egm_backward_fits(N, Na) || !labor_dist_forward_fits(N, Na))
+        return fail(AIY_BAD_ARG, "Jacobian: the transition passes' arrays exceed one CU's LDS "
+                                 "(aiy_labor_transition_batch's fit rules)");
+    AIY_TRY(check_expect_shape(N, Na));
+    AIY_TRY(check_fake_news(T, 2, N * Na, h));
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    if (!std::isfinite(phi) || !(phi > 0))
+        return fail(AIY_BAD_ARG, "phi must be positive and finite");
+    if (!std::isfinite(theta) || theta == 0)
+        return fail(AIY_BAD_ARG, "theta must be finite and not 0");
+    if (!std::isfinite(r_ss) || !(1 + r_ss > 0) || !std::isfinite(r_ss + h))
+        return fail(AIY_BAD_ARG, "r_ss must be finite with 1 + r_ss > 0");
+    if (!std::isfinite(w_ss) || !std::isfinite(w_ss + h))
+        return fail(AIY_BAD_ARG, "w_ss must be finite");
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    double *da, *ds, *dP;
+    AIY_TRY(stage_common(c, a_grid, s, P, N, Na, &da, &ds, &dP));
+    const size_t n = (size_t)N * Na, tt = (size_t)T * T;
+    const int64_t C3 = 3, CF = 3 * T;
+    // the three price paths: the steady state, r[T-1] + h, w[T-1] + h
+    std::vector<double> rp(C3 * (T + 1), r_ss), wp(C3 * T, w_ss), y0(n);
+    rp[(size_t)(T + 1) + T - 1] = r_ss + h;
+    wp[2 * (size_t)T + T - 1] = w_ss + h;
+    for (size_t e = 0; e < n; ++e) y0[e] = a_grid[e % Na];
+    double *dr, *dw, *dc, *dl0, *dy, *dyh, *dpk, *dpl, *dK, *dH, *dl1, *dEa, *dEh, *dF, *dJ, *dG;
+    int *bres, *fres;
+    AIY_TRY(c->up_own("tr_r", std::move(rp), &dr));
+    AIY_TRY(c->up_own("tr_w", std::move(wp), &dw));
+    AIY_TRY(c->up_own("ssj_y0", std::move(y0), &dy));
+    AIY_TRY(c->up("tr_pcT", policy_c, n, &dc));
+    AIY_TRY(c->up("tr_l0", lambda, n, &dl0));
+    AIY_TRY(c->room("ssj_yh", n, &dyh));
+    AIY_TRY(c->room("tr_pk", (size_t)C3 * T * n, &dpk));
+    AIY_TRY(c->room("tr_pl", (size_t)C3 * T * n, &dpl));
+    AIY_TRY(c->room("tr_K", (size_t)CF * 2, &dK));
+    AIY_TRY(c->room("tr_H", (size_t)CF, &dH));
+    AIY_TRY(c->room("ssj_lam1", (size_t)CF * n, &dl1));
+    AIY_TRY(c->room("ssj_E", (size_t)T * n, &dEa));
+    AIY_TRY(c->room("ssj_Eh", (size_t)T * n, &dEh));
+    AIY_TRY(c->room("ssj_F", 4 * tt, &dF));   // F_Kr, F_Kw, F_Hr, F_Hw
+    AIY_TRY(c->room("ssj_J", 4 * tt, &dJ));   // J_Kr, J_Kw, J_Hr, J_Hw
+    AIY_TRY(c->room("ssj_G", 2 * tt, &dG));
+    AIY_TRY(c->room("ssj_bres", 2 * (size_t)C3, &bres));
+    AIY_TRY(c->room("ssj_fres", 2 * (size_t)CF, &fres));
+    Events ev;  // the stages' boundaries as the stream dispatches them
+    if (stage_ms) AIY_TRY(ev.create(5, 0));
+    auto mark = [&](int q) -> int {
+        if (stage_ms) AIY_HIP(hipEventRecord(ev[q], c->st));
+        return AIY_OK;
+    };
+    AIY_TRY(mark(0));
+    {  // 1. the policies of an agent who learns of the change s periods ahead: pk, pl [3][T][N][Na]
+        EgmBackwardArgs A{};
+        A.N = (int)N; A.Na = (int)Na; A.C = (int)C3; A.T = (int)T;
+        A.ns = is_int_ge(sigma, 1.0) ? (int)sigma : 0;
+        A.beta = beta; A.sigma = sigma; A.amin = amin; A.phi = phi; A.theta = theta;
+        A.r = dr; A.w = dw; A.pcT = dc; A.pcT_stride = 0;
+        A.a = da; A.s = ds; A.P = dP; A.pk = dpk; A.pl = dpl; A.pc = nullptr;
+        A.status = bres; A.fail_t = bres + C3;
+        AIY_TRY(launch_labor_egm_backward_batch(A, c->st));
+    }
+    AIY_TRY(mark(1));
+    {  // 2. one push of the steady state's λ through each of them: Λ1 [3][T][N][Na], H1 [3][T]
+        DistForwardArgs A{};
+        A.N = (int)N; A.Na = (int)Na; A.C = (int)CF; A.T = 1;
+        A.pk = dpk; A.pl = dpl; A.lam0 = dl0; A.lam0_stride = 0;
+        A.a = da; A.s = ds; A.P = dP; A.K = dK; A.H = dH; A.lamT = dl1;
+        A.status = fres; A.fail_t = fres + CF; A.skip = nullptr;
+        AIY_TRY(launch_labor_dist_forward_batch(A, c->st));
+    }
+    AIY_TRY(mark(2));
+    // 3. the expectation vectors of assets and of hours under the base path's period-0 policies
+    AIY_TRY(launch_ssj_hours_outcome(ds, dpl, (int)N, (int)Na, dyh, c->st));
+    AIY_TRY(expect_dev(N, Na, 1, T, dpk, dy, true, da, dP, dEa, c->st));
+    AIY_TRY(expect_dev(N, Na, 1, T, dpk, dyh, true, da, dP, dEh, c->st));
+    AIY_TRY(mark(3));
+    // 4, 5. the fake-news matrices and the Jacobians: capital, then hours
+    AIY_TRY(fake_news_dev(T, 2, (int64_t)n, dEa, dl1, h, dF, dJ, c->st));
+    {
+        SsjHoursArgs A{};
+        A.T = (int)T; A.n_in = 2; A.n = (int)n; A.h = h;
+        A.Eh = dEh; A.lam1 = dl1; A.H1 = dH; A.G = dG; A.F = dF + 2 * tt; A.J = dJ + 2 * tt;
+        AIY_TRY(launch_ssj_hours_jacobian(A, c->st));
+    }
+    AIY_TRY(mark(4));
+    std::vector<int> hb(C3), hf(CF);
+    double* const Jo[4] = {J_Kr, J_Kw, J_Hr, J_Hw};
+    double* const Fo[4] = {F_Kr, F_Kw, F_Hr, F_Hw};
+    for (int q = 0; q < 4; ++q) {
+        AIY_TRY(c->down(Jo[q], dJ + q * tt, tt));
+        if (Fo[q]) AIY_TRY(c->down(Fo[q], dF + q * tt, tt));
+    }
+    if (E_a) AIY_TRY(c->down(E_a, dEa, (size_t)T * n));
+    if (E_h) AIY_TRY(c->down(E_h, dEh, (size_t)T * n));
+    AIY_TRY(c->down(hb.data(), bres, (size_t)C3));
+    AIY_TRY(c->down(hf.data(), fres, (size_t)CF));
+    AIY_TRY(c->sync());
+    int sb = 0, sf = 0;
+    for (int v : hb) sb |= v;
+    for (int v : hf) sf |= v;
+    *backward_status = sb;
+    *forward_status = sf;
+    if (sb | sf) {  // a pass stopped: nothing downstream of it is a derivative
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int q = 0; q < 4; ++q)
+            for (size_t e = 0; e < tt; ++e) Jo[q][e] = nan;
     }
     if (stage_ms)
         for (int q = 0; q < 4; ++q) {

@@ -179,6 +179,26 @@ __global__ void ssj_jacobian_kernel(SsjFakeNewsArgs A) {
     }
 }
 
+// y(j, a) = s_j·pl(j, a): the hours outcome of a labour policy
+__global__ void ssj_hours_outcome_kernel(const double* __restrict__ s,
+                                         const double* __restrict__ pl, int n, int Na,
+                                         double* __restrict__ y) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) y[e] = s[e / Na] * pl[e];
+}
+
+// F_H of input x = blockIdx.y: row 0 from the one-step hours, row t >= 1 = row t − 1 of G
+__global__ void ssj_hours_rows_kernel(SsjHoursArgs A) {
+    const int T = A.T;
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (size_t)T * T) return;
+    const int t = (int)(q / T), s = (int)(q - (size_t)t * T);
+    const int x = blockIdx.y;
+    const size_t o = (size_t)x * T * T;
+    A.F[o + q] = t == 0 ? (A.H1[(size_t)(x + 1) * T + (T - 1 - s)] - A.H1[T - 1 - s]) / A.h
+                        : A.G[o + q - T];
+}
+
 int launch_dist_expect_batch(const DistExpectArgs& A, hipStream_t st) {
     if (A.C < 1 || A.T < 1) return fail(AIY_BAD_SHAPE, "expectation pass needs C >= 1 and T >= 1");
     if (!dist_expect_fits(A.N, A.Na))
@@ -202,6 +222,34 @@ int launch_ssj_fake_news(const SsjFakeNewsArgs& A, hipStream_t st) {
     ssj_fake_news_kernel<<<dim3(nt, nt, A.n_in), 256, 0, st>>>(A);
     AIY_HIP(hipGetLastError());
     ssj_jacobian_kernel<<<dim3((2 * A.T - 1 + 255) / 256, A.n_in), 256, 0, st>>>(A);
+    AIY_HIP(hipGetLastError());
+    return AIY_OK;
+}
+
+int launch_ssj_hours_outcome(const double* s, const double* pl, int N, int Na, double* y,
+                             hipStream_t st) {
+    const int n = N * Na;
+    if (N < 1 || Na < 1) return fail(AIY_BAD_SHAPE, "hours outcome needs N >= 1 and Na >= 1");
+    ssj_hours_outcome_kernel<<<(n + 255) / 256, 256, 0, st>>>(s, pl, n, Na, y);
+    AIY_HIP(hipGetLastError());
+    return AIY_OK;
+}
+
+int launch_ssj_hours_jacobian(const SsjHoursArgs& A, hipStream_t st) {
+    if (A.T < 1 || A.T > kSsjMaxT || A.n_in < 1 || A.n_in > 65535 || A.n < 1)
+        return fail(AIY_BAD_SHAPE, "hours Jacobian needs 1 <= T <= 32768, 1 <= n_in <= 65535 "
+                                   "and n >= 1");
+    SsjFakeNewsArgs B{};
+    B.T = A.T; B.n_in = A.n_in; B.n = A.n; B.h = A.h;
+    B.E = A.Eh; B.lam1 = A.lam1; B.F = A.G; B.J = A.J;
+    const int nt = (A.T + kFnTile - 1) / kFnTile;
+    ssj_fake_news_kernel<<<dim3(nt, nt, A.n_in), 256, 0, st>>>(B);
+    AIY_HIP(hipGetLastError());
+    const size_t tt = (size_t)A.T * A.T;
+    ssj_hours_rows_kernel<<<dim3((unsigned)((tt + 255) / 256), A.n_in), 256, 0, st>>>(A);
+    AIY_HIP(hipGetLastError());
+    B.F = A.F;
+    ssj_jacobian_kernel<<<dim3((2 * A.T - 1 + 255) / 256, A.n_in), 256, 0, st>>>(B);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }

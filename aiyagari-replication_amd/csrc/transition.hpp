@@ -30,9 +30,21 @@ struct EgmBackwardArgs {
     int* status;  // device [C]: 0 ok, 1 = â not increasing at period fail_t (periods below it
                   // are not computed; the period's own outputs are undefined)
     int* fail_t;  // device [C]: −1, or the period that stopped the path
+    // the labour pass only (launch_labor_egm_backward_batch)
+    double phi, theta;
+    double* pl;  // device [C][T][N][Na]
 };
 inline bool egm_backward_fits(int64_t N, int64_t Na) { return egm_batch_fits(N, Na, false); }
 int launch_egm_backward_batch(const EgmBackwardArgs& A, hipStream_t st);
+
+// The backward pass of the endogenous-labour economy (A5): the two-rate labour step
+//   RHS, c̃ as above,  ℓ̃ = labor_dev(c̃, w[t]·s_j),  â = ((c̃ + a) − (w[t]·s_j)·ℓ̃)/(1 + r[t]),
+//   g = interp1(â_j, c̃_j, a),  a < amin → g = amin,  pc_t = g,  pl_t = labor_dev(g, w[t]·s_j),
+//   k = ((1 + r[t])·a + (w[t]·s_j)·pl_t) − g,  pk_t = k < 0 ? 0 : k
+// — egm_fused_kernel's labour operations with r split in two.  LDS as egm_solve_batch_kernel<true>:
+// policy_c, â and c̃ [N][Na] each (a_grid is read from global memory).
+inline bool labor_egm_backward_fits(int64_t N, int64_t Na) { return egm_batch_fits(N, Na, true); }
+int launch_labor_egm_backward_batch(const EgmBackwardArgs& A, hipStream_t st);
 
 // The forward pass: from λ₀, t = 0 … T−1: the lottery plan of pk_t, K[t] = Σ λ_t·a, one push.
 struct DistForwardArgs {
@@ -49,6 +61,11 @@ struct DistForwardArgs {
     int* fail_t;         // device [C]
     const int* skip;     // device [C] (nullable): a non-zero entry — the backward pass's status —
                          // leaves the path alone but for K, all NaN; status and fail_t not written
+    // the pass with hours only (launch_labor_dist_forward_batch): H[c][t] = Σ λ_t·(s_j·pl_t),
+    // t = 0 … T−1, in K[t]'s summation order; NaN where K[t] is NaN
+    const double* pl;    // device [C][T][N][Na]
+    const double* s;     // device [N]
+    double* H;           // device [C][T]
 };
 // LDS of one workgroup: dist_solve_batch_kernel<true>'s (λ, mass, lottery weights, run offsets,
 // scratch) and a_grid.  The period's keys and the partial sums of K live in the mass array, which
@@ -61,5 +78,15 @@ inline bool dist_forward_fits(int64_t N, int64_t Na) {
     return dist_batch_fits(N, Na, true) && dist_forward_lds_bytes(N, Na) <= kDistBatchMaxLds;
 }
 int launch_dist_forward_batch(const DistForwardArgs& A, hipStream_t st);
+// The pass with hours: the same LDS and s [16] after a_grid.  The block sums of H follow those of
+// K in the mass array's spare half (2·⌈n/256⌉ <= ⌊n/2⌋ from n = 4 on); at n < 4 the one block sum
+// of H sits in the scratch's unused key slot.
+inline size_t labor_dist_forward_lds_bytes(int64_t N, int64_t Na) {
+    return dist_forward_lds_bytes(N, Na) + sizeof(double) * 16;
+}
+inline bool labor_dist_forward_fits(int64_t N, int64_t Na) {
+    return dist_forward_fits(N, Na) && labor_dist_forward_lds_bytes(N, Na) <= kDistBatchMaxLds;
+}
+int launch_labor_dist_forward_batch(const DistForwardArgs& A, hipStream_t st);
 
 }  // namespace aiy

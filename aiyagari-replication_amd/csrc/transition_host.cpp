@@ -3,6 +3,9 @@
 // the period policies stay on the device, the host reads K, status and fail_t).
 // Arrays are [N][Na] rows per (path, period) — the EGM scripts' Na x N column-major; P is
 // column-major in the host tier (staged as rows), row-major in the device tier.
+// The endogenous-labour economy (A5) has the same five entries, aiy_labor_*: the backward pass
+// also yields policy_l, the forward pass also H[c][t] = Σ λ_t·(s_j·policy_l_t), the hours in
+// efficiency units.
 // Everything a host entry can refuse it refuses before it asks for a device.
 #include <hip/hip_runtime.h>
 
@@ -57,6 +60,26 @@ static int check_forward_shape(int64_t N, int64_t Na) {
     return AIY_OK;
 }
 
+static int check_labor_shapes(int64_t N, int64_t Na, bool backward, bool forward) {
+    if (N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need N >= 1 and Na >= 2");
+    if (backward && !labor_egm_backward_fits(N, Na))
+        return fail(AIY_BAD_ARG, "backward labour EGM pass: a path's arrays exceed one CU's LDS "
+                                 "(N <= 16, Na <= 1024, 3·N·Na doubles within 160 KiB)");
+    if (forward && !labor_dist_forward_fits(N, Na))
+        return fail(AIY_BAD_ARG, "forward pass with hours: a path's arrays exceed one CU's LDS "
+                                 "(N <= 16, 8·N·Na·3 + 4·N·(Na+1) + 8·Na + 2.3 KB within 160 KiB)");
+    return AIY_OK;
+}
+
+// the labour first-order condition's parameters: l = (w s u'(c) / phi)^(1/theta)
+static int check_labor_params(double phi, double theta) {
+    if (!std::isfinite(phi) || !(phi > 0))
+        return fail(AIY_BAD_ARG, "phi must be positive and finite");
+    if (!std::isfinite(theta) || theta == 0)
+        return fail(AIY_BAD_ARG, "theta must be finite and not 0");
+    return AIY_OK;
+}
+
 // the backward launch; every pointer is the device's
 static int backward_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r, const double* w,
                         const double* pcT, bool shared, const double* a, const double* s,
@@ -71,6 +94,39 @@ static int backward_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r, const
     A.a = a; A.s = s; A.P = P; A.pk = pk; A.pc = pc; A.status = status; A.fail_t = fail_t;
     AIY_TRY(ws_timing_begin(ws, st));
     AIY_TRY(launch_egm_backward_batch(A, st));
+    return ws_timing_end(ws, st);
+}
+
+static int labor_backward_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r, const double* w,
+                              const double* pcT, bool shared, const double* a, const double* s,
+                              const double* P, double beta, double sigma, double phi,
+                              double theta, double amin, double* pk, double* pl, double* pc,
+                              int* status, int* fail_t, hipStream_t st) {
+    EgmBackwardArgs A{};
+    A.N = (int)ws->N; A.Na = (int)ws->Na; A.C = (int)C; A.T = (int)T;
+    A.ns = is_int_ge(sigma, 1.0) ? (int)sigma : 0;
+    A.beta = beta; A.sigma = sigma; A.amin = amin; A.phi = phi; A.theta = theta;
+    A.r = r; A.w = w; A.pcT = pcT;
+    A.pcT_stride = shared ? 0 : (size_t)ws->N * ws->Na;
+    A.a = a; A.s = s; A.P = P; A.pk = pk; A.pl = pl; A.pc = pc;
+    A.status = status; A.fail_t = fail_t;
+    AIY_TRY(ws_timing_begin(ws, st));
+    AIY_TRY(launch_labor_egm_backward_batch(A, st));
+    return ws_timing_end(ws, st);
+}
+
+static int labor_forward_dev(aiy_ws* ws, int64_t C, int64_t T, const double* pk, const double* pl,
+                             const double* lam0, bool shared, const double* a, const double* s,
+                             const double* P, double* K, double* H, double* lamT, int* status,
+                             int* fail_t, const int* skip, hipStream_t st) {
+    DistForwardArgs A{};
+    A.N = (int)ws->N; A.Na = (int)ws->Na; A.C = (int)C; A.T = (int)T;
+    A.pk = pk; A.pl = pl; A.lam0 = lam0;
+    A.lam0_stride = shared ? 0 : (size_t)ws->N * ws->Na;
+    A.a = a; A.s = s; A.P = P; A.K = K; A.H = H; A.lamT = lamT;
+    A.status = status; A.fail_t = fail_t; A.skip = skip;
+    AIY_TRY(ws_timing_begin(ws, st));
+    AIY_TRY(launch_labor_dist_forward_batch(A, st));
     return ws_timing_end(ws, st);
 }
 
@@ -247,6 +303,161 @@ int aiy_transition_batch(int64_t C, int64_t T, const double* r, const double* w,
     AIY_TRY(forward_dev(c->ws, C, T, dpk, dl0, lambda0_shared != 0, D.a, D.P, dK, nullptr, D.res,
                         D.res + C, D.res, c->st));
     AIY_TRY(c->down(K, dK, (size_t)C * (T + 1)));
+    AIY_TRY(c->down(status, D.res, (size_t)C));
+    AIY_TRY(c->down(fail_t, D.res + C, (size_t)C));
+    return c->sync();
+}
+
+int aiy_labor_egm_backward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r,
+                                     const double* w, const double* pc_T, int pc_T_shared,
+                                     const double* a_grid, const double* s, const double* P,
+                                     double beta, double sigma, double phi, double theta,
+                                     double amin, double* policy_k, double* policy_l,
+                                     double* policy_c, int32_t* status, int32_t* fail_t,
+                                     void* stream) {
+    if (!ws || !r || !w || !pc_T || !a_grid || !s || !P || !policy_k || !policy_l || !status ||
+        !fail_t)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_counts(C, T));
+    AIY_TRY(check_labor_shapes(ws->N, ws->Na, true, false));
+    AIY_TRY(check_labor_params(phi, theta));
+    AIY_TRY(check_prices(C, T, r, w));
+    hipStream_t st = (hipStream_t)stream;
+    TransitionBlocks& tb = ws->transition;
+    AIY_TRY(tb.ensure((size_t)C, (size_t)T));
+    const size_t nr = (size_t)C * (T + 1), nw = (size_t)C * T;
+    std::memcpy(tb.hrw.get(), r, sizeof(double) * nr);
+    std::memcpy(tb.hrw.get() + nr, w, sizeof(double) * nw);
+    AIY_HIP(hipMemcpyAsync(tb.rw, tb.hrw, sizeof(double) * (nr + nw), hipMemcpyHostToDevice, st));
+    AIY_TRY(labor_backward_dev(ws, C, T, tb.rw, tb.rw + nr, pc_T, pc_T_shared != 0, a_grid, s, P,
+                               beta, sigma, phi, theta, amin, policy_k, policy_l, policy_c, tb.res,
+                               tb.res + C, st));
+    return read_results(ws, C, status, fail_t, st);
+}
+
+int aiy_labor_dist_forward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* policy_k,
+                                     const double* policy_l, const double* lambda0,
+                                     int lambda0_shared, const double* a_grid, const double* s,
+                                     const double* P, double* K, double* H, double* lambda_T,
+                                     int32_t* status, int32_t* fail_t, void* stream) {
+    if (!ws || !policy_k || !policy_l || !lambda0 || !a_grid || !s || !P || !K || !H || !status ||
+        !fail_t)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_counts(C, T));
+    AIY_TRY(check_labor_shapes(ws->N, ws->Na, false, true));
+    hipStream_t st = (hipStream_t)stream;
+    TransitionBlocks& tb = ws->transition;
+    AIY_TRY(tb.ensure((size_t)C, (size_t)T));
+    AIY_TRY(labor_forward_dev(ws, C, T, policy_k, policy_l, lambda0, lambda0_shared != 0, a_grid,
+                              s, P, K, H, lambda_T, tb.res, tb.res + C, nullptr, st));
+    return read_results(ws, C, status, fail_t, st);
+}
+
+int aiy_labor_egm_backward_batch(int64_t C, int64_t T, const double* r, const double* w,
+                                 const double* pc_T, int pc_T_shared, const double* a_grid,
+                                 const double* s, const double* P, int64_t N, int64_t Na,
+                                 double beta, double sigma, double phi, double theta, double amin,
+                                 double* policy_k, double* policy_l, double* policy_c,
+                                 int32_t* status, int32_t* fail_t) {
+    if (!r || !w || !pc_T || !s || !P || !policy_k || !policy_l || !status || !fail_t)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_counts(C, T));
+    AIY_TRY(check_labor_shapes(N, Na, true, false));
+    AIY_TRY(check_labor_params(phi, theta));
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    AIY_TRY(check_prices(C, T, r, w));
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    TransitionStaged D;
+    AIY_TRY(stage_transition(c, C, a_grid, s, P, N, Na, &D));
+    const size_t n = (size_t)N * Na, np = (size_t)C * T * n;
+    double *dr, *dw, *dc, *dpk, *dpl, *dpc = nullptr;
+    AIY_TRY(c->up("tr_r", r, (size_t)C * (T + 1), &dr));
+    AIY_TRY(c->up("tr_w", w, (size_t)C * T, &dw));
+    AIY_TRY(c->up("tr_pcT", pc_T, pc_T_shared ? n : n * (size_t)C, &dc));
+    AIY_TRY(c->room("tr_pk", np, &dpk));
+    AIY_TRY(c->room("tr_pl", np, &dpl));
+    if (policy_c) AIY_TRY(c->room("tr_pc", np, &dpc));
+    AIY_TRY(labor_backward_dev(c->ws, C, T, dr, dw, dc, pc_T_shared != 0, D.a, D.s, D.P, beta,
+                               sigma, phi, theta, amin, dpk, dpl, dpc, D.res, D.res + C, c->st));
+    AIY_TRY(c->down(policy_k, dpk, np));
+    AIY_TRY(c->down(policy_l, dpl, np));
+    if (policy_c) AIY_TRY(c->down(policy_c, dpc, np));
+    AIY_TRY(c->down(status, D.res, (size_t)C));
+    AIY_TRY(c->down(fail_t, D.res + C, (size_t)C));
+    return c->sync();
+}
+
+int aiy_labor_dist_forward_batch(int64_t C, int64_t T, const double* policy_k,
+                                 const double* policy_l, const double* lambda0,
+                                 int lambda0_shared, const double* a_grid, const double* s,
+                                 const double* P, int64_t N, int64_t Na, double* K, double* H,
+                                 double* lambda_T, int32_t* status, int32_t* fail_t) {
+    if (!policy_k || !policy_l || !lambda0 || !s || !P || !K || !H || !status || !fail_t)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_counts(C, T));
+    AIY_TRY(check_labor_shapes(N, Na, false, true));
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    TransitionStaged D;
+    AIY_TRY(stage_transition(c, C, a_grid, s, P, N, Na, &D));
+    const size_t n = (size_t)N * Na;
+    double *dpk, *dpl, *dl0, *dK, *dH, *dlT = nullptr;
+    AIY_TRY(c->up("tr_pk", policy_k, (size_t)C * T * n, &dpk));
+    AIY_TRY(c->up("tr_pl", policy_l, (size_t)C * T * n, &dpl));
+    AIY_TRY(c->up("tr_l0", lambda0, lambda0_shared ? n : n * (size_t)C, &dl0));
+    AIY_TRY(c->room("tr_K", (size_t)C * (T + 1), &dK));
+    AIY_TRY(c->room("tr_H", (size_t)C * T, &dH));
+    if (lambda_T) AIY_TRY(c->room("tr_lT", n * (size_t)C, &dlT));
+    AIY_TRY(labor_forward_dev(c->ws, C, T, dpk, dpl, dl0, lambda0_shared != 0, D.a, D.s, D.P, dK,
+                              dH, dlT, D.res, D.res + C, nullptr, c->st));
+    AIY_TRY(c->down(K, dK, (size_t)C * (T + 1)));
+    AIY_TRY(c->down(H, dH, (size_t)C * T));
+    if (lambda_T) AIY_TRY(c->down(lambda_T, dlT, n * (size_t)C));
+    AIY_TRY(c->down(status, D.res, (size_t)C));
+    AIY_TRY(c->down(fail_t, D.res + C, (size_t)C));
+    return c->sync();
+}
+
+int aiy_labor_transition_batch(int64_t C, int64_t T, const double* r, const double* w,
+                               const double* pc_T, int pc_T_shared, const double* lambda0,
+                               int lambda0_shared, const double* a_grid, const double* s,
+                               const double* P, int64_t N, int64_t Na, double beta, double sigma,
+                               double phi, double theta, double amin, double* K, double* H,
+                               int32_t* status, int32_t* fail_t) {
+    if (!r || !w || !pc_T || !lambda0 || !s || !P || !K || !H || !status || !fail_t)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    AIY_TRY(check_counts(C, T));
+    AIY_TRY(check_labor_shapes(N, Na, true, true));
+    AIY_TRY(check_labor_params(phi, theta));
+    AIY_TRY(check_grid_strict(a_grid, Na));
+    AIY_TRY(check_prices(C, T, r, w));
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    TransitionStaged D;
+    AIY_TRY(stage_transition(c, C, a_grid, s, P, N, Na, &D));
+    const size_t n = (size_t)N * Na;
+    double *dr, *dw, *dc, *dl0, *dpk, *dpl, *dK, *dH;
+    AIY_TRY(c->up("tr_r", r, (size_t)C * (T + 1), &dr));
+    AIY_TRY(c->up("tr_w", w, (size_t)C * T, &dw));
+    AIY_TRY(c->up("tr_pcT", pc_T, pc_T_shared ? n : n * (size_t)C, &dc));
+    AIY_TRY(c->up("tr_l0", lambda0, lambda0_shared ? n : n * (size_t)C, &dl0));
+    AIY_TRY(c->room("tr_pk", (size_t)C * T * n, &dpk));
+    AIY_TRY(c->room("tr_pl", (size_t)C * T * n, &dpl));
+    AIY_TRY(c->room("tr_K", (size_t)C * (T + 1), &dK));
+    AIY_TRY(c->room("tr_H", (size_t)C * T, &dH));
+    AIY_TRY(labor_backward_dev(c->ws, C, T, dr, dw, dc, pc_T_shared != 0, D.a, D.s, D.P, beta,
+                               sigma, phi, theta, amin, dpk, dpl, nullptr, D.res, D.res + C,
+                               c->st));
+    // a path the backward pass stopped keeps its status and fail_t; its K and H are NaN
+    AIY_TRY(labor_forward_dev(c->ws, C, T, dpk, dpl, dl0, lambda0_shared != 0, D.a, D.s, D.P, dK,
+                              dH, nullptr, D.res, D.res + C, D.res, c->st));
+    AIY_TRY(c->down(K, dK, (size_t)C * (T + 1)));
+    AIY_TRY(c->down(H, dH, (size_t)C * T));
     AIY_TRY(c->down(status, D.res, (size_t)C));
     AIY_TRY(c->down(fail_t, D.res + C, (size_t)C));
     return c->sync();

@@ -383,3 +383,337 @@ def aiyagari_transition_newton(ss, Z, T=None, jac=None, tol=1e-6, max_iter=50, b
         live = upd[~done]
     r, w = price(K, Z)
     return dict(K=K, r=r, w=w, rounds=rounds, status=status, resid=resid)
+
+
+# ------------------------------------------------------------- the endogenous-labour economy
+def labor_egm_backward_batch(r, w, pc_T, a_grid, s, P, beta, sigma, phi, theta, amin,
+                             want_pc=True):
+    """aiy_labor_egm_backward_batch: egm_backward_batch for the labour economy (A5).  Returns
+    dict(policy_k, policy_l, policy_c [C][T][N][Na] (policy_c None unless want_pc), status [C],
+    fail_t [C])."""
+    r, w, n_c, T = _paths(r, w)
+    a, s, P = _f(a_grid), _f(s), np.asfortranarray(P, dtype=np.float64)
+    N, Na = s.size, a.size
+    pcT, shared = _start(pc_T, n_c, N, Na, "pc_T")
+    pk, pl = np.empty((n_c, T, N, Na)), np.empty((n_c, T, N, Na))
+    pc = np.empty((n_c, T, N, Na)) if want_pc else None
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_labor_egm_backward_batch(i64(n_c), i64(T), ptr(r), ptr(w), ptr(pcT), ip(shared),
+                                             ptr(a), ptr(s), ptr(P), i64(N), i64(Na), d(beta),
+                                             d(sigma), d(phi), d(theta), d(amin), ptr(pk), ptr(pl),
+                                             ptr(pc), ptr(st), ptr(ft)))
+    return dict(policy_k=pk, policy_l=pl, policy_c=pc, status=st, fail_t=ft)
+
+
+def labor_dist_forward_batch(policy_k, policy_l, lam0, a_grid, s, P, want_lam=True):
+    """aiy_labor_dist_forward_batch: dist_forward_batch and the hours in efficiency units,
+    H[c][t] = Σ λ_t·(s_j·policy_l[c][t]).  Returns dict(K [C][T+1], H [C][T], lam_T, status,
+    fail_t); on status 2, K and H beyond fail_t are NaN."""
+    pk, pl = _f(policy_k), _f(policy_l)
+    if pk.ndim != 4 or pl.shape != pk.shape:
+        raise ValueError("policy_k and policy_l must be [C][T][N][Na]")
+    n_c, T, N, Na = pk.shape
+    a, s, P = _f(a_grid), _f(s), np.asfortranarray(P, dtype=np.float64)
+    l0, shared = _start(lam0, n_c, N, Na, "lam0")
+    K, H = np.empty((n_c, T + 1)), np.empty((n_c, T))
+    lT = np.empty((n_c, N, Na)) if want_lam else None
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_labor_dist_forward_batch(i64(n_c), i64(T), ptr(pk), ptr(pl), ptr(l0),
+                                             ip(shared), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
+                                             ptr(K), ptr(H), ptr(lT), ptr(st), ptr(ft)))
+    return dict(K=K, H=H, lam_T=lT, status=st, fail_t=ft)
+
+
+def labor_transition_batch(r, w, pc_T, lam0, a_grid, s, P, beta, sigma, phi, theta, amin):
+    """aiy_labor_transition_batch: both passes on one stream, the period policies staying on the
+    device.  Returns (K [C][T+1], H [C][T], status [C], fail_t [C]); a path with status 1 has K
+    and H all NaN."""
+    r, w, n_c, T = _paths(r, w)
+    a, s, P = _f(a_grid), _f(s), np.asfortranarray(P, dtype=np.float64)
+    N, Na = s.size, a.size
+    pcT, pshared = _start(pc_T, n_c, N, Na, "pc_T")
+    l0, lshared = _start(lam0, n_c, N, Na, "lam0")
+    K, H = np.empty((n_c, T + 1)), np.empty((n_c, T))
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_labor_transition_batch(i64(n_c), i64(T), ptr(r), ptr(w), ptr(pcT),
+                                           ip(pshared), ptr(l0), ip(lshared), ptr(a), ptr(s),
+                                           ptr(P), i64(N), i64(Na), d(beta), d(sigma), d(phi),
+                                           d(theta), d(amin), ptr(K), ptr(H), ptr(st), ptr(ft)))
+    return K, H, st, ft
+
+
+def labor_egm_backward_batch_dev(ws, r, w, pc_T, a_grid, s, P, beta, sigma, phi, theta, amin,
+                                 policy_k, policy_l, policy_c=None, stream=None):
+    """aiy_labor_egm_backward_batch_dev (torch tensors; r [C][T+1] and w [C][T] numpy): as
+    egm_backward_batch_dev, with policy_l [C][T][N][Na].  Returns (status [C], fail_t [C])."""
+    from ._capi import stream_handle
+    r, w, n_c, T = _paths(r, w)
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_labor_egm_backward_batch_dev(
+        ws.handle, i64(n_c), i64(T), ptr(r), ptr(w), ptr(pc_T), ip(1 if pc_T.dim() == 2 else 0),
+        ptr(a_grid), ptr(s), ptr(P), d(beta), d(sigma), d(phi), d(theta), d(amin), ptr(policy_k),
+        ptr(policy_l), ptr(policy_c), ptr(st), ptr(ft), stream_handle(stream)))
+    return st, ft
+
+
+def labor_dist_forward_batch_dev(ws, policy_k, policy_l, lam0, a_grid, s, P, K, H, lam_T=None,
+                                 stream=None):
+    """aiy_labor_dist_forward_batch_dev (torch tensors): as dist_forward_batch_dev, with policy_l
+    [C][T][N][Na], s [N] and H [C][T].  Returns (status [C], fail_t [C])."""
+    from ._capi import stream_handle
+    n_c, T = int(policy_k.shape[0]), int(policy_k.shape[1])
+    st, ft = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_labor_dist_forward_batch_dev(
+        ws.handle, i64(n_c), i64(T), ptr(policy_k), ptr(policy_l), ptr(lam0),
+        ip(1 if lam0.dim() == 2 else 0), ptr(a_grid), ptr(s), ptr(P), ptr(K), ptr(H), ptr(lam_T),
+        ptr(st), ptr(ft), stream_handle(stream)))
+    return st, ft
+
+
+def prices_from_ratio(kappa, Z, ss):
+    """The price paths of capital per effective hour κ = K/H and TFP paths Z (same shape),
+    anchored to the steady state ss (r, w, K, H), x = κ/κ_ss, κ_ss = K_ss/H_ss:
+        r_t = r_ss + (r_ss + δ)·(Z_t·x_t^(α−1) − 1),   w_t = w_ss·Z_t·x_t^α.
+    At κ = κ_ss, Z = 1 this returns r_ss and w_ss exactly."""
+    kappa, Z = np.asarray(kappa, np.float64), np.asarray(Z, np.float64)
+    alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]
+    x = kappa / (ss["K"] / ss["H"])
+    r = ss["r"] + (ss["r"] + delta) * (Z * _pow(x, alpha - 1) - 1.0)
+    return r, ss["w"] * Z * _pow(x, alpha)
+
+
+def hours_sum(lam, policy_l, s):
+    """H = Σ λ·(s_j·policy_l) of [N][Na] arrays, on the host."""
+    return float(np.sum(_f(lam) * (_f(s)[:, None] * _f(policy_l))))
+
+
+def labor_excess(K, H, r, alpha, delta):
+    """K − H·(α/(r+δ))^(1/(1−α)): the capital market's excess supply at hours H."""
+    return K - H * (alpha / (r + delta)) ** (1 / (1 - alpha))
+
+
+def steady_state_labor(cal, phi=1.0, theta=1.0, r_low=0.0, r_high=None, rounds=12, width=7,
+                       tol=1e-11, max_iter=5000, k_tol=1e-8, device="cuda"):
+    """The stationary equilibrium of the labour economy (A5): dict(r, w, K, H, policy_c, policy_l,
+    policy_k, lam ([N][Na]), cal, phi, theta).  r by bisection on K_s(r) − H(r)·(α/(r+δ))^(1/(1−α)) at
+    w = cb.wage(r): a round's `width` equally spaced candidates go through ONE batched labour EGM
+    solve (egm_solve_batch_dev, labor=True) and ONE batched stationary-distribution solve
+    (dist_stationary_batch_dev); H is summed on the host from the returned λ and policy_l.  The
+    bracket shrinks to the sub-interval where the excess changes sign (× 1/(width+1) per round)
+    and the search stops once a candidate's |excess| <= k_tol.  Not the script's K_d, which uses
+    the exogenous aggregate cal["labor"]: here labour demand is the hours households supply."""
+    import torch
+    from . import calibration as cb
+    from . import ge_batch as gb
+    from .dist import dist_stationary_batch_dev
+    from .egm import egm_solve_batch_dev
+    from .vfi import Workspace
+    a, s, P = _f(cal["a_grid"]), _f(cal["s"]), _f(cal["P"])
+    N, Na = s.size, a.size
+    alpha, delta = cal["alpha"], cal["delta"]
+    wage = lambda r: cb.wage(r, alpha, delta)
+    f64 = dict(dtype=torch.float64, device=device)
+    da, ds, dP = (torch.as_tensor(x, **f64) for x in (a, s, P))
+    ws = Workspace(N, Na)
+    r0 = 0.04  # the labour script's starting policy_c (Aiyagari_Endogenous_Labor_EGM.m:58)
+    guess = np.tile((1 + r0) * a + wage(r0) * np.mean(s), (N, 1))
+    uni = np.full((N, Na), 1.0 / (N * Na))
+
+    def many(rr):
+        rr = np.ascontiguousarray(rr, np.float64)
+        n_c = rr.size
+        pc = torch.as_tensor(np.tile(guess, (n_c, 1, 1)), **f64)
+        pk, pl = torch.empty_like(pc), torch.empty_like(pc)
+        _, _, st = egm_solve_batch_dev(ws, rr, wage(rr), pc, da, ds, dP, cal["beta"], cal["sigma"],
+                                       cal["amin"], tol, max_iter, pk, labor=True, phi=phi,
+                                       theta=theta, policy_l=pl)
+        if st.any():
+            raise RuntimeError(f"labour EGM solve: status {st} at r = {rr}")
+        lam = torch.empty_like(pc)
+        Ks = torch.empty(n_c, **f64)
+        dist_stationary_batch_dev(ws, torch.as_tensor(np.tile(uni, (n_c, 1, 1)), **f64), da, dP,
+                                  lam, policy_k=pk, tol=gb.HIST_TOL, max_iter=gb.HIST_MAX_ITER,
+                                  k_supply=Ks)
+        torch.cuda.synchronize()
+        lam, pl, pc, pk, Ks = (x.cpu().numpy() for x in (lam, pl, pc, pk, Ks))
+        H = np.array([hours_sum(lam[q], pl[q], s) for q in range(n_c)])
+        ex = np.array([labor_excess(Ks[q], H[q], rr[q], alpha, delta) for q in range(n_c)])
+        return ex, Ks, H, pc, pl, pk, lam
+    try:
+        lo, hi = r_low, (1 / cal["beta"] - 1 if r_high is None else r_high)
+        best = None
+        for _ in range(rounds):
+            rr = lo + (hi - lo) * np.arange(1, width + 1) / (width + 1)
+            ex, Ks, H, pc, pl, pk, lam = many(rr)
+            q = int(np.argmin(np.abs(ex)))
+            if best is None or abs(ex[q]) < abs(best[0]):
+                best = (ex[q], rr[q], Ks[q], H[q], pc[q], pl[q], pk[q], lam[q])
+            if abs(best[0]) <= k_tol:
+                break
+            up = np.flatnonzero(ex > 0)  # the excess supply rises with r
+            j = int(up[0]) if up.size else width
+            lo, hi = (rr[j - 1] if j > 0 else lo), (rr[j] if j < width else hi)
+    finally:
+        ws.close()
+    _, r, K, H, pc, pl, pk, lam = best
+    return dict(r=float(r), w=float(wage(r)), K=float(K), H=float(H), policy_c=pc, policy_l=pl,
+                policy_k=pk, lam=lam, cal=cal, phi=phi, theta=theta)
+
+
+def jacobian_labor(ss, T, h=1e-4, stage_ms=None):
+    """aiy_ssj_jacobian_labor: the sequence-space Jacobians of the labour economy's capital and
+    hours paths around the steady state ss (steady_state_labor's dict).  Returns dict(J_Kr, J_Kw
+    (J[t][s] = ∂K_{t+1}/∂x_s), J_Hr, J_Hw (J[t][s] = ∂H_t/∂x_s), F_Kr, F_Kw, F_Hr, F_Hw [T][T],
+    E_a, E_h [T][N][Na], status (backward, forward)).  A non-zero status: the J are NaN."""
+    cal = ss["cal"]
+    a, s, P = _f(cal["a_grid"]), _f(cal["s"]), np.asfortranarray(cal["P"], dtype=np.float64)
+    N, Na = s.size, a.size
+    pc, lam = _f(ss["policy_c"]), _f(ss["lam"])
+    if pc.shape != (N, Na) or lam.shape != (N, Na):
+        raise ValueError("ss['policy_c'] and ss['lam'] must be [N][Na]")
+    Tn = max(int(T), 0)
+    M = {k: np.empty((Tn, Tn)) for k in ("J_Kr", "J_Kw", "J_Hr", "J_Hw", "F_Kr", "F_Kw", "F_Hr",
+                                         "F_Hw")}
+    E_a, E_h = np.empty((Tn, N, Na)), np.empty((Tn, N, Na))
+    sb, sf = ip(0), ip(0)
+    check(lib().aiy_ssj_jacobian_labor(
+        ptr(pc), ptr(lam), d(ss["r"]), d(ss["w"]), ptr(a), ptr(s), ptr(P), i64(N), i64(Na),
+        d(cal["beta"]), d(cal["sigma"]), d(ss["phi"]), d(ss["theta"]), d(cal["amin"]), i64(T), d(h),
+        ptr(M["J_Kr"]), ptr(M["J_Kw"]), ptr(M["J_Hr"]), ptr(M["J_Hw"]), ptr(M["F_Kr"]),
+        ptr(M["F_Kw"]), ptr(M["F_Hr"]), ptr(M["F_Hw"]), ptr(E_a), ptr(E_h), ctypes.byref(sb),
+        ctypes.byref(sf), ptr(stage_ms)))
+    return dict(M, E_a=E_a, E_h=E_h, status=(sb.value, sf.value))
+
+
+def _ratio_slopes(ss):
+    """∂r/∂κ, ∂w/∂κ, ∂r/∂Z, ∂w/∂Z of prices_from_ratio at the steady state."""
+    alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]
+    k_ss = ss["K"] / ss["H"]
+    return ((ss["r"] + delta) * (alpha - 1) / k_ss, ss["w"] * alpha / k_ss, ss["r"] + delta,
+            ss["w"])
+
+
+def _labor_response(ss, jac, r_x, w_x):
+    """∂κ_supply/∂x for prices moving with slopes (r_x, w_x): κ_s,t = K_t/H_t, K_t the
+    Jacobian's row t − 1 (K_0 is given), so
+    ((J′_Kr·r_x + J′_Kw·w_x) − κ_ss·(J_Hr·r_x + J_Hw·w_x))/H_ss with J′_K = J_K shifted a row."""
+    JK = _f(jac["J_Kr"]) * r_x + _f(jac["J_Kw"]) * w_x
+    JH = _f(jac["J_Hr"]) * r_x + _f(jac["J_Hw"]) * w_x
+    JKs = np.zeros_like(JK)
+    JKs[1:] = JK[:-1]
+    return (JKs - (ss["K"] / ss["H"]) * JH) / ss["H"]
+
+
+def _labor_newton_matrix(ss, jac):
+    """M − I, M = ∂κ_supply/∂κ at the steady state."""
+    r_k, w_k, _, _ = _ratio_slopes(ss)
+    M = _labor_response(ss, jac, r_k, w_k)
+    return M - np.eye(M.shape[0])
+
+
+def impulse_response_labor(ss, jac, dZ):
+    """The linear responses (dK [C][T+1], dH [C][T]) to the TFP paths 1 + dZ, dZ [C][T]:
+    (I − M)·dκ = N_Z·dZ with M of aiyagari_labor_transition_newton and N_Z = ∂κ_supply/∂Z, then
+    dr = r_κ·dκ + r_Z·dZ, dw likewise, dK[1:] = J_Kr·dr + J_Kw·dw, dH = J_Hr·dr + J_Hw·dw.  Each
+    path is its own solve."""
+    dZ = np.atleast_2d(np.asarray(dZ, np.float64))
+    r_k, w_k, r_Z, w_Z = _ratio_slopes(ss)
+    A = -_labor_newton_matrix(ss, jac)
+    NZ = _labor_response(ss, jac, r_Z, w_Z)
+    if dZ.shape[1] != A.shape[0]:
+        raise ValueError("dZ must be [C][T] with the Jacobian's T")
+    dK, dH = np.zeros((dZ.shape[0], dZ.shape[1] + 1)), np.zeros(dZ.shape)
+    for c in range(dZ.shape[0]):
+        dk = np.linalg.solve(A, NZ @ dZ[c])
+        dr, dw = r_k * dk + r_Z * dZ[c], w_k * dk + w_Z * dZ[c]
+        dK[c, 1:] = _f(jac["J_Kr"]) @ dr + _f(jac["J_Kw"]) @ dw
+        dH[c] = _f(jac["J_Hr"]) @ dr + _f(jac["J_Hw"]) @ dw
+    return dK, dH
+
+
+def _labor_driver(ss, Z, T, tol, max_iter, backend, update):
+    """The lockstep loop both labour drivers share; update(κ_c, κ_supply_c) -> the next κ_c."""
+    Z = np.atleast_2d(np.asarray(Z, np.float64))
+    if T is None:
+        T = Z.shape[1]
+    if Z.shape[1] != T or T < 1:
+        raise ValueError("Z must be [C][T] with T >= 1")
+    run = labor_transition_batch if backend is None else backend
+    cal = ss["cal"]
+    n_c = Z.shape[0]
+    kap = np.full((n_c, T), float(ss["K"]) / float(ss["H"]))
+    K, H = np.full((n_c, T + 1), np.nan), np.full((n_c, T), np.nan)
+    rounds, status = np.zeros(n_c, np.int64), np.zeros(n_c, np.int32)
+    resid = np.full(n_c, np.nan)
+    live = np.arange(n_c)
+
+    def price(kc, Zc):
+        r, w = prices_from_ratio(kc, Zc, ss)
+        return np.concatenate([r, np.full((len(kc), 1), float(ss["r"]))], axis=1), w
+    for _ in range(max_iter):
+        if live.size == 0:
+            break
+        r, w = price(kap[live], Z[live])
+        Ks, Hs, st, _ = run(r, w, ss["policy_c"], ss["lam"], cal["a_grid"], cal["s"], cal["P"],
+                            cal["beta"], cal["sigma"], ss["phi"], ss["theta"], cal["amin"])
+        rounds[live] += 1
+        status[live] = st
+        K[live], H[live] = Ks, Hs
+        ok = st == 0
+        ks = Ks[ok][:, :T] / Hs[ok]
+        gap = np.full(live.size, np.nan)
+        gap[ok] = np.max(np.abs(ks - kap[live[ok]]), axis=1)
+        resid[live] = gap
+        upd = live[ok]
+        done = gap[ok] < tol
+        for q in np.flatnonzero(~done):
+            kap[upd[q]] = update(kap[upd[q]], ks[q])
+        live = upd[~done]
+    r, w = price(kap, Z)
+    return dict(K=K, H=H, kappa=kap, r=r, w=w, rounds=rounds, status=status, resid=resid)
+
+
+def aiyagari_labor_transition(ss, Z, T=None, damp=0.05, tol=1e-6, max_iter=1000, backend=None):
+    """The labour economy's transitions after C unexpected TFP paths Z [C][T] from the steady
+    state ss (steady_state_labor's dict), by a lockstep damped fixed point.  The unknown is
+    capital per effective hour κ_t = K_t/H_t, t = 0 … T−1 — hours jump on impact, so K_0 being
+    given does not pin the date-0 prices, and prices depend on K and H through κ alone.  Every
+    path starts at κ ≡ κ_ss; a round prices the paths still running (prices_from_ratio; the
+    terminal rate is r_ss), runs them through ONE labor_transition_batch call — backend(r, w,
+    pc_T, lam0, a_grid, s, P, beta, sigma, phi, theta, amin) -> (K, H, status, fail_t), the GPU's
+    by default — sets κ_s = K[:T]/H and updates κ ← (1 − damp)·κ + damp·κ_s.  A path stops when
+    max_t |κ_s − κ| < tol (measured before the update), on a non-zero status, or after max_iter
+    rounds.  A path's arithmetic does not depend on the others in its batch.
+    damp defaults to 0.05, not the exogenous driver's 0.5: with elastic hours the map κ → κ_s
+    overshoots — the leading eigenvalue of M = ∂κ_s/∂κ is real and negative — and the damped
+    update contracts only for damp < 2/(1 + ρ(M)).  ρ(M) grows with the horizon: measured on the
+    labour script's calibration 2.9, 7.5, 14.4 and 20.4 at T = 30, 60, 120 and 240 (N = 3,
+    Na = 60), 7.4 at T = 60 (N = 7, Na = 100).  So 0.5 diverges from T ≈ 30 on (gaps 0.82, 5.8, 50
+    after 2, 4, 6 rounds at T = 60), 0.1 from T ≈ 240 on; 0.05 covers ρ < 39 and takes about 270
+    rounds to 1e-8 on a 1 % AR(0.9) TFP path, where the Newton driver takes 5.
+    Returns dict(K [C][T+1], H [C][T] (the last round's supply), kappa [C][T], r [C][T+1],
+    w [C][T], rounds [C], status [C], resid [C])."""
+    return _labor_driver(ss, Z, T, tol, max_iter, backend,
+                         lambda k, ks: (1 - damp) * k + damp * ks)
+
+
+def aiyagari_labor_transition_newton(ss, Z, T=None, jac=None, tol=1e-6, max_iter=50,
+                                     backend=None):
+    """aiyagari_labor_transition with a Newton update from the steady state's sequence-space
+    Jacobians: the same arguments, rounds, stopping rule and return dict; the update is
+        κ ← κ − (M − I)⁻¹·(κ_s − κ),
+    M = ((J′_Kr·r_κ + J′_Kw·w_κ) − κ_ss·(J_Hr·r_κ + J_Hw·w_κ))/H_ss, J′_K[0] = 0 and J′_K[t] =
+    J_K[t−1], r_κ = (r_ss + δ)(α − 1)/κ_ss, w_κ = w_ss·α/κ_ss.  The same (M − I) serves every
+    round and path; a path's update is its own single-right-hand-side solve.
+    jac: jacobian_labor(ss, T)'s dict (computed once when None)."""
+    Tn = np.atleast_2d(np.asarray(Z)).shape[1] if T is None else T
+    if jac is None:
+        jac = jacobian_labor(ss, Tn)
+    if any(np.shape(jac[k]) != (Tn, Tn) for k in ("J_Kr", "J_Kw", "J_Hr", "J_Hw")):
+        raise ValueError("jac must hold J_Kr, J_Kw, J_Hr and J_Hw [T][T]")
+    A = _labor_newton_matrix(ss, jac)
+    if not np.isfinite(A).all():
+        raise ValueError(f"the Jacobian is not finite (jacobian_labor()'s status: "
+                         f"{jac.get('status')})")
+    return _labor_driver(ss, Z, T, tol, max_iter, backend,
+                         lambda k, ks: k - np.linalg.solve(A, ks - k))

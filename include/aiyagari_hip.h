@@ -624,7 +624,7 @@ int aiy_ws_dist_batch_counts(aiy_ws* ws, int64_t* launches, int64_t* fallback_so
  *   g = interp1(a^_j, a_grid, a_grid(a), linear, extrap), g < amin -> amin,
  *   pk_t = g,  pc_t = ((1 + r[t]) a_grid(a) + w[t] s_j) - g
  * — aiy_egm_step's operations with r split in two: on r[t+1] == r[t] it equals that step bit for
- * bit.  (The labour step, A5, has no transition entry.)
+ * bit.  The labour step, A5, has the same entries under aiy_labor_* (below).
  *
  * Backward pass on device: r host [C][T+1] (r[c][T]: the terminal rate of period T-1's Euler
  * equation), w host [C][T]; pc_T device [C][N][Na], or one [N][Na] for all paths (pc_T_shared);
@@ -715,6 +715,82 @@ int aiy_ssj_jacobian(const double* policy_c, const double* lambda, double r_ss, 
                      int64_t Na, double beta, double sigma, double amin, int64_t T, double h,
                      double* J_r, double* J_w, double* F_r, double* F_w, double* E,
                      int32_t* backward_status, int32_t* forward_status, double* stage_ms);
+
+/* ---- Transition paths of the endogenous-labour economy (A5; new).  The same five entries and the
+ * same conventions as above.  Fit rules (else AIY_BAD_ARG, no per-step fallback):
+ *   backward: N <= 16, Na <= 1024, 3·N·Na doubles + 2.4 KB within 160 KiB;
+ *   forward:  N <= 16, 8·N·Na·3 + 4·N·(Na+1) + 8·Na + 2.3 KB within 160 KiB.
+ * The two-rate labour step of period t (pc_next = the consumption policy of period t+1;
+ * labor(c, x) = ((x u'(c)) / phi)^(1/theta), the power skipped when 1/theta == 1):
+ *   RHS(j,a) = sum_m ((beta(1+r[t+1])) P(j,m)) u'(pc_next(m,a)),  c~ = RHS^(-1/sigma),
+ *   l~ = labor(c~, w[t] s_j),  a^(j,a) = ((c~ + a_grid(a)) - (w[t] s_j) l~) / (1 + r[t]),
+ *   g = interp1(a^_j, c~_j, a_grid(a), linear, extrap),  a_grid(a) < amin -> g = amin,  pc_t = g,
+ *   pl_t = labor(g, w[t] s_j),  k = ((1 + r[t]) a_grid(a) + (w[t] s_j) pl_t) - g,
+ *   pk_t = k < 0 ? 0 : k
+ * — aiy_labor_egm_step's operations with r split in two: on r[t+1] == r[t] it equals that step
+ * bit for bit.  policy_k, policy_l, policy_c (nullable): [C][T][N][Na].  status 1 as
+ * aiy_egm_backward_batch_dev.  Also refused before any launch: phi <= 0 or not finite, theta = 0
+ * or not finite. */
+int aiy_labor_egm_backward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* r,
+                                     const double* w, const double* pc_T, int pc_T_shared,
+                                     const double* a_grid, const double* s, const double* P,
+                                     double beta, double sigma, double phi, double theta,
+                                     double amin, double* policy_k, double* policy_l,
+                                     double* policy_c, int32_t* status, int32_t* fail_t,
+                                     void* stream);
+/* aiy_dist_forward_batch_dev and the hours in efficiency units, H[c][t] = sum lambda_t(j,a)
+ * (s_j policy_l[c][t](j,a)), t = 0 .. T-1 (device [C][T]): the inner product rounded first, the
+ * summation order K[t]'s.  K[t] and H[t] are formed before period t's monotonicity check: on
+ * status 2 both are written up to fail_t and NaN beyond.  K, lambda_T, status and fail_t equal
+ * aiy_dist_forward_batch_dev's on the same policy_k bit for bit. */
+int aiy_labor_dist_forward_batch_dev(aiy_ws* ws, int64_t C, int64_t T, const double* policy_k,
+                                     const double* policy_l, const double* lambda0,
+                                     int lambda0_shared, const double* a_grid, const double* s,
+                                     const double* P, double* K, double* H, double* lambda_T,
+                                     int32_t* status, int32_t* fail_t, void* stream);
+/* The same two passes on host arrays (P column-major N x N).  Also refused before any launch: an
+ * a_grid that is not strictly increasing. */
+int aiy_labor_egm_backward_batch(int64_t C, int64_t T, const double* r, const double* w,
+                                 const double* pc_T, int pc_T_shared, const double* a_grid,
+                                 const double* s, const double* P, int64_t N, int64_t Na,
+                                 double beta, double sigma, double phi, double theta, double amin,
+                                 double* policy_k, double* policy_l, double* policy_c,
+                                 int32_t* status, int32_t* fail_t);
+int aiy_labor_dist_forward_batch(int64_t C, int64_t T, const double* policy_k,
+                                 const double* policy_l, const double* lambda0,
+                                 int lambda0_shared, const double* a_grid, const double* s,
+                                 const double* P, int64_t N, int64_t Na, double* K, double* H,
+                                 double* lambda_T, int32_t* status, int32_t* fail_t);
+/* Both passes on one stream, the period policies staying on the device: K [C][T+1], H [C][T],
+ * status and fail_t [C].  A path the backward pass stopped (status 1) has K and H all NaN. */
+int aiy_labor_transition_batch(int64_t C, int64_t T, const double* r, const double* w,
+                               const double* pc_T, int pc_T_shared, const double* lambda0,
+                               int lambda0_shared, const double* a_grid, const double* s,
+                               const double* P, int64_t N, int64_t Na, double beta, double sigma,
+                               double phi, double theta, double amin, double* K, double* H,
+                               int32_t* status, int32_t* fail_t);
+/* The Jacobians of K_{t+1} and of H_t in r_s and w_s around a steady state of the labour economy
+ * (host arrays; policy_c, lambda: [N][Na]; P column-major), everything between the inputs and the
+ * J matrices staying on the device:
+ *   1. aiy_labor_egm_backward_batch's pass of 3 paths from policy_c (as aiy_ssj_jacobian);
+ *   2. aiy_labor_dist_forward_batch's pass of the 3T period policies, one push each from lambda:
+ *      Lambda1 [3][T][N][Na] and H1 [3][T], the hours of each period policy under lambda;
+ *   3. the expectation vectors under the base path's period-0 policy_k of y0 = a_grid (E_a) and
+ *      of y0 = s_j policy_l_base,0 (E_h);
+ *   4. with D_x[s] = (Lambda1[x+1][T-1-s] - Lambda1[0][T-1-s]) / h:
+ *        F_K[x][t][s] = E_a[t]·D_x[s];
+ *        F_H[x][0][s] = (H1[x+1][T-1-s] - H1[0][T-1-s]) / h  (hours jump on impact),
+ *        F_H[x][t][s] = E_h[t-1]·D_x[s] for t >= 1  (aiy_ssj_fake_news's contraction);
+ *   5. J[t][s] = F[t][s] + J[t-1][s-1] down each diagonal, for all four.
+ * J_Kr, J_Kw: [T][T], J[t][s] = dK_{t+1}/dx_s; J_Hr, J_Hw: [T][T], J[t][s] = dH_t/dx_s.  The four
+ * F [T][T], E_a and E_h [T][N][Na] are nullable.  Status words and stage_ms as aiy_ssj_jacobian. */
+int aiy_ssj_jacobian_labor(const double* policy_c, const double* lambda, double r_ss,
+                           double w_ss, const double* a_grid, const double* s, const double* P,
+                           int64_t N, int64_t Na, double beta, double sigma, double phi,
+                           double theta, double amin, int64_t T, double h, double* J_Kr,
+                           double* J_Kw, double* J_Hr, double* J_Hw, double* F_Kr, double* F_Kw,
+                           double* F_Hr, double* F_Hw, double* E_a, double* E_h,
+                           int32_t* backward_status, int32_t* forward_status, double* stage_ms);
 
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
