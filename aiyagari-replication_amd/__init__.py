@@ -31,11 +31,18 @@ from .transition import (aiyagari_labor_transition, aiyagari_labor_transition_ne
                          labor_dist_forward_batch_dev, labor_egm_backward_batch,
                          labor_egm_backward_batch_dev, labor_transition_batch, prices_from_ratio,
                          steady_state_labor)
+from . import estimation
+from .estimation import (ar1_loglik, ar1_ma, ar1_mle, autocovariance_batch, ge_jacobians,
+                         ge_jacobians_labor, loglik_batch, loglik_batch_dev, ma_batch,
+                         ma_batch_dev, moments)
 from . import vfi
 from .vfi import (Workspace, labor_solve_batch_dev, labor_vfi_solve, labor_vfi_sweep,
                   solve_batch_dev, vfi_solve, vfi_sweep)
 
-__all__ = ["aiyagari_labor_transition", "aiyagari_labor_transition_newton",
+__all__ = ["estimation", "ar1_loglik", "ar1_ma", "ar1_mle", "autocovariance_batch", "ge_jacobians",
+           "ge_jacobians_labor", "loglik_batch", "loglik_batch_dev", "ma_batch", "ma_batch_dev",
+           "moments",
+           "aiyagari_labor_transition", "aiyagari_labor_transition_newton",
            "impulse_response_labor", "jacobian_labor", "labor_dist_forward_batch",
            "labor_dist_forward_batch_dev", "labor_egm_backward_batch",
            "labor_egm_backward_batch_dev", "labor_transition_batch", "prices_from_ratio",

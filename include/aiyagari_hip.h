@@ -792,6 +792,44 @@ int aiy_ssj_jacobian_labor(const double* policy_c, const double* lambda, double 
                            double* F_Hr, double* F_Hw, double* E_a, double* E_h,
                            int32_t* backward_status, int32_t* forward_status, double* stage_ms);
 
+/* ---- Second moments and the Gaussian likelihood from the sequence-space Jacobian (new).
+ * G: [n_o][T][T], G[o][t][s] = dX_{o,t}/dZ_s, the general-equilibrium Jacobians of n_o observables
+ * in the shock (estimation.ge_jacobians); dZ: [C][T], the MA coefficients of C shock processes.
+ *   m[c][o][t] = sum_s G[o][t][s] dZ[c][s]   (fp64 matrix cores, s ascending in steps of 4)
+ * m: [C][n_o][T].  An entry's bits depend on row (o, t) of G and row c of dZ only — not on C, n_o
+ * or the run (no atomics).  Refused: n_o outside [1, 64], T outside [1, 32768], C outside
+ * [1, 2^24].  The device entry only enqueues on `stream`. */
+int aiy_ssj_ma_batch_dev(int64_t n_o, int64_t T, int64_t C, const double* G, const double* dZ,
+                         double* m, void* stream);
+int aiy_ssj_ma_batch(int64_t n_o, int64_t T, int64_t C, const double* G, const double* dZ,
+                     double* m);
+/* Autocovariances and log-likelihood of C candidates, ONE workgroup per candidate, everything in
+ * LDS.  m: [C][n_o][T]; y: [L][n_o], the observed deviations from the steady state, shared by all
+ * candidates; me_var: the measurement-error variances, [n_o] (me_var_shared) or [C][n_o].  With
+ * n = L n_o and row i = t n_o + o, no fused multiply-adds:
+ *   1. Gamma[l][o][p] = sum_{u=0}^{T-1-l} m[o][u+l] m[p][u], u ascending from +0; l >= T: +0;
+ *   2. V[(t,o)][(t',p)] = Gamma[t-t'][o][p] for t >= t' (lower triangle), me_var[o] added to the
+ *      diagonal's Gamma[0][o][o]; z = y;
+ *   3. j = 0 .. n-1: d_j = V[j][j]; unless d_j > 0: status 1, fail j, loglik NaN, stop; else
+ *      w_i = V[i][j], l_i = w_i / d_j (i = j+1 .. n-1, and z's w = z_j, l = z_j / d_j),
+ *      V[i][k] = V[i][k] - (l_i w_k) for j < k <= i, z_k = z_k - (l w_k) for k > j;
+ *   4. logdet = sum_j aiy_log(d_j), quad = sum_j (z_j z_j) / d_j, j ascending from +0;
+ *      loglik = -0.5 ((n 1.8378770664093453 + logdet) + quad); status 0, fail -1.
+ * loglik: [C]; status, fail: [C]; Gamma (nullable): [C][L][n_o][n_o], step 1's sums without
+ * me_var; d (nullable): [C][n], the pivots (on status 1: up to d[fail], NaN beyond).  y NULL:
+ * step 1 only — Gamma is the result and me_var, loglik, status and fail are not touched.
+ * A candidate's bits do not depend on C, on the other candidates or on the run; a NaN in m[c]
+ * gives candidate c status 1 and stays there.  Fit rule (else AIY_BAD_ARG, no fallback):
+ * max(n(n+1)/2, n_o T) + n n_o + 3n + 2 doubles within 160 KiB (n_o = 1: L <= 197).  The host
+ * entry also refuses a me_var that is negative or not finite.  The device entry only enqueues. */
+int aiy_ssj_loglik_batch_dev(int64_t C, int64_t n_o, int64_t T, int64_t L, const double* m,
+                             const double* y, const double* me_var, int me_var_shared,
+                             double* loglik, int32_t* status, int32_t* fail, double* Gamma,
+                             double* d, void* stream);
+int aiy_ssj_loglik_batch(int64_t C, int64_t n_o, int64_t T, int64_t L, const double* m,
+                         const double* y, const double* me_var, int me_var_shared, double* loglik,
+                         int32_t* status, int32_t* fail, double* Gamma, double* d);
+
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
  * arrays (the layout of Krusell_Smith_VFI.m's `value`).  Each call writes only the shard's
