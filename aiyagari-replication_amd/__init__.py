@@ -35,13 +35,17 @@ from . import estimation
 from .estimation import (ar1_loglik, ar1_ma, ar1_mle, autocovariance_batch, ge_jacobians,
                          ge_jacobians_labor, loglik_batch, loglik_batch_dev, ma_batch,
                          ma_batch_dev, moments)
+from .estimation import (dense_solve_batch, dense_solve_batch_dev, ge_ma_batch,
+                         structural_loglik)
+from .transition import jacobian_batch
 from . import vfi
 from .vfi import (Workspace, labor_solve_batch_dev, labor_vfi_solve, labor_vfi_sweep,
                   solve_batch_dev, vfi_solve, vfi_sweep)
 
 __all__ = ["estimation", "ar1_loglik", "ar1_ma", "ar1_mle", "autocovariance_batch", "ge_jacobians",
            "ge_jacobians_labor", "loglik_batch", "loglik_batch_dev", "ma_batch", "ma_batch_dev",
-           "moments",
+           "moments", "dense_solve_batch", "dense_solve_batch_dev", "ge_ma_batch",
+           "structural_loglik", "jacobian_batch",
            "aiyagari_labor_transition", "aiyagari_labor_transition_newton",
            "impulse_response_labor", "jacobian_labor", "labor_dist_forward_batch",
            "labor_dist_forward_batch_dev", "labor_egm_backward_batch",

@@ -227,7 +227,8 @@ __device__ __forceinline__ void wave_max_to_slots(bool ok, double d,
     wave_max_to_slots(ok, d, slots, (int)blockIdx.x);
 }
 
-inline int is_int_ge(double x, double lo) {
+// (host and device: the batched backward pass picks an economy's fast power with it)
+__host__ __device__ inline int is_int_ge(double x, double lo) {
     return x >= lo && x < 64 && (double)(int64_t)x == x;
 }
 

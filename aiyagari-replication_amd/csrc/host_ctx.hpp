@@ -136,6 +136,12 @@ struct Staging {
     }
 };
 
+// The host tier's staging cap (bytes of device memory one chunk of a chunked host entry may
+// ask for): aiy_dense_solve_batch and aiy_ssj_jacobian_batch process their C systems or economies
+// in chunks of at most max(1, kBatchStageBytes / (bytes per system or economy)) when the caller
+// passes chunk = 0.
+constexpr size_t kBatchStageBytes = (size_t)4 << 30;
+
 struct HostCtx : Staging<DevStream> {
     aiy_ws* ws = nullptr;
     ~HostCtx();

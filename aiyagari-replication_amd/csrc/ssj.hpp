@@ -23,6 +23,9 @@ struct DistExpectArgs {
     const double* a;
     const double* P;    // row-major
     double* E;          // device [C][T][N][Na]
+    // One economy per steady state (all zero: one economy, as above): c reads its policy at
+    // pk + c·pk_stride (pk_stride = 0: N·Na), a + c·a_stride and P + c·P_stride.
+    size_t pk_stride, a_stride, P_stride;
 };
 // LDS of one workgroup: E_t, G_t, wl (N·Na doubles each), lo (N·Na ints, padded to 8 bytes) and
 // P [16][16].  a_grid sits in G's array while the plan is built.
@@ -48,8 +51,14 @@ struct SsjFakeNewsArgs {
     const double* lam1;  // device [n_in + 1][T][n], block 0 the base
     double* F;           // device [n_in][T][T]
     double* J;           // device [n_in][T][T]
+    // C economies in one launch (C = 0: one, as above): E [C][T][n], lam1 [C][n_in + 1][T][n],
+    // F and J [C][n_in][T][T]; the launch grid's third dimension is c·n_in + x, so C·n_in <=
+    // 65,535.  An entry's MFMA chain is the same whatever C.
+    int C;
 };
 constexpr int kSsjMaxT = 32768;  // T·T entries and the launch grid stay below 2^31 / 65,536
+// economies per chunk of aiy_ssj_jacobian_batch: 2 inputs each in the grid's third dimension
+constexpr int64_t kSsjBatchMaxChunk = 32767;
 int launch_ssj_fake_news(const SsjFakeNewsArgs& A, hipStream_t st);
 
 // The labour economy's hours H_t = Σ λ_t·(s_j·pl_t) respond to news at date 0 already (the policy

@@ -1,15 +1,18 @@
 // Sequence-space Jacobian entry points: the expectation vectors (aiy_dist_expect_batch[_dev]), the
 // fake-news contraction (aiy_ssj_fake_news[_dev]) and the whole Jacobian of the capital path in
 // r and w on one stream (aiy_ssj_jacobian: the period policies, Λ1, E and F stay on the device),
+// the same of C economies, each stage one launch over a chunk of them (aiy_ssj_jacobian_batch),
 // and the same of the labour economy's capital and hours paths (aiy_ssj_jacobian_labor).
 // Arrays are [N][Na] rows per block; P is column-major in the host tier (staged as rows),
 // row-major in the device tier.  Everything a host entry can refuse it refuses before it asks
 // for a device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "aiy_common.hpp"
@@ -227,6 +230,165 @@ int aiy_ssj_jacobian(const double* policy_c, const double* lambda, double r_ss, 
             AIY_HIP(hipEventElapsedTime(&ms, ev[q], ev[q + 1]));
             stage_ms[q] = ms;
         }
+    return AIY_OK;
+}
+
+int aiy_ssj_jacobian_batch(int64_t C, const double* policy_c, const double* lambda,
+                           const double* r_ss, const double* w_ss, const double* a_grid,
+                           const double* s, const double* P, int64_t N, int64_t Na,
+                           const double* beta, const double* sigma, const double* amin, int64_t T,
+                           double h, double* J_r, double* J_w, double* F_r, double* F_w, double* E,
+                           int32_t* backward_status, int32_t* forward_status, double* stage_ms,
+                           int64_t chunk) {
+    if (!policy_c || !lambda || !r_ss || !w_ss || !a_grid || !s || !P || !beta || !sigma ||
+        !amin || !J_r || !J_w || !backward_status || !forward_status)
+        return fail(AIY_BAD_ARG, "NULL argument");
+    if (C < 1 || C > (1ll << 24)) return fail(AIY_BAD_SHAPE, "need 1 <= C <= 2^24");
+    if (N < 1 || Na < 2) return fail(AIY_BAD_SHAPE, "need N >= 1 and Na >= 2");
+    if (!egm_backward_fits(N, Na) || !dist_forward_fits(N, Na))
+        return fail(AIY_BAD_ARG, "Jacobian: the transition passes' arrays exceed one CU's LDS "
+                                 "(aiy_transition_batch's fit rules)");
+    AIY_TRY(check_expect_shape(N, Na));
+    AIY_TRY(check_fake_news(T, 2, N * Na, h));
+    if (chunk < 0 || chunk > kSsjBatchMaxChunk)
+        return fail(AIY_BAD_ARG, "chunk must be in [0, 32767] (0: the default)");
+    for (int64_t e = 0; e < C; ++e) {
+        const long long q = (long long)e;
+        if (const int rc = check_grid_strict(a_grid + e * Na, Na)) {
+            const std::string why = aiy_last_error();
+            return fail(rc, "economy %lld: %s", q, why.c_str());
+        }
+        if (!std::isfinite(r_ss[e]) || !(1 + r_ss[e] > 0) || !std::isfinite(r_ss[e] + h))
+            return fail(AIY_BAD_ARG, "economy %lld: r_ss must be finite with 1 + r_ss > 0", q);
+        if (!std::isfinite(w_ss[e]) || !std::isfinite(w_ss[e] + h))
+            return fail(AIY_BAD_ARG, "economy %lld: w_ss must be finite", q);
+        if (!std::isfinite(beta[e]) || !(beta[e] > 0))
+            return fail(AIY_BAD_ARG, "economy %lld: beta must be positive and finite", q);
+        if (!std::isfinite(sigma[e]) || !(sigma[e] > 0))
+            return fail(AIY_BAD_ARG, "economy %lld: sigma must be positive and finite", q);
+        if (!std::isfinite(amin[e])) return fail(AIY_BAD_ARG, "economy %lld: amin must be finite", q);
+    }
+    const size_t n = (size_t)N * Na, tt = (size_t)T * T, NN = (size_t)N * N;
+    if (chunk == 0) {  // pk and Λ1 (3·T·n each), E (T·n), F and J (2·T² each) of an economy
+        const size_t per = sizeof(double) * (7 * (size_t)T * n + 4 * tt);
+        chunk = (int64_t)std::max<size_t>(1, kBatchStageBytes / per);
+    }
+    chunk = std::min(std::min(chunk, C), kSsjBatchMaxChunk);
+    chunk = std::min(chunk, std::max<int64_t>(1, ((1ll << 31) - 1) / (3 * T)));  // 3·T paths each
+    std::lock_guard<std::mutex> lk(host_mutex());
+    HostCtx* c;
+    AIY_TRY(get_ctx(N, Na, 1, &c));
+    Events ev;  // the stages' boundaries as the stream dispatches them, chunk by chunk
+    if (stage_ms) {
+        AIY_TRY(ev.create(5, 0));
+        for (int q = 0; q < 4; ++q) stage_ms[q] = 0;
+    }
+    auto mark = [&](int q) -> int {
+        if (stage_ms) AIY_HIP(hipEventRecord(ev[q], c->st));
+        return AIY_OK;
+    };
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t e0 = 0; e0 < C; e0 += chunk) {
+        const int64_t m = std::min(chunk, C - e0), C3 = 3 * m, CF = 3 * m * T;
+        // an economy's three price paths: the steady state, r[T-1] + h, w[T-1] + h
+        std::vector<double> rp(C3 * (T + 1)), wp(C3 * T), y0(m * n), prm(3 * m);
+        for (int64_t i = 0; i < m; ++i) {
+            const int64_t e = e0 + i;
+            std::fill_n(rp.begin() + 3 * i * (T + 1), 3 * (T + 1), r_ss[e]);
+            std::fill_n(wp.begin() + 3 * i * T, 3 * T, w_ss[e]);
+            rp[(size_t)(3 * i + 1) * (T + 1) + T - 1] = r_ss[e] + h;
+            wp[(size_t)(3 * i + 2) * T + T - 1] = w_ss[e] + h;
+            for (size_t k = 0; k < n; ++k) y0[i * n + k] = a_grid[e * Na + k % Na];
+            prm[3 * i] = beta[e];
+            prm[3 * i + 1] = sigma[e];
+            prm[3 * i + 2] = amin[e];
+        }
+        double *da, *ds, *dP, *dprm, *dr, *dw, *dc, *dl0, *dy, *dpk, *dK, *dl1, *dE, *dF, *dJ;
+        int *bres, *fres;
+        AIY_TRY(c->up("ssjb_a", a_grid + e0 * Na, (size_t)m * Na, &da));
+        AIY_TRY(c->up("ssjb_s", s + e0 * N, (size_t)m * N, &ds));
+        AIY_TRY(c->up_rows("ssjb_P", P + e0 * NN, N, N, m, &dP));
+        AIY_TRY(c->up_own("ssjb_prm", std::move(prm), &dprm));
+        AIY_TRY(c->up_own("tr_r", std::move(rp), &dr));
+        AIY_TRY(c->up_own("tr_w", std::move(wp), &dw));
+        AIY_TRY(c->up_own("ssj_y0", std::move(y0), &dy));
+        AIY_TRY(c->up("tr_pcT", policy_c + e0 * n, (size_t)m * n, &dc));
+        AIY_TRY(c->up("tr_l0", lambda + e0 * n, (size_t)m * n, &dl0));
+        AIY_TRY(c->room("tr_pk", (size_t)C3 * T * n, &dpk));
+        AIY_TRY(c->room("tr_K", (size_t)CF * 2, &dK));
+        AIY_TRY(c->room("ssj_lam1", (size_t)CF * n, &dl1));
+        AIY_TRY(c->room("ssj_E", (size_t)m * T * n, &dE));
+        AIY_TRY(c->room("ssj_F", 2 * tt * m, &dF));
+        AIY_TRY(c->room("ssj_J", 2 * tt * m, &dJ));
+        AIY_TRY(c->room("ssj_bres", 2 * (size_t)C3, &bres));
+        AIY_TRY(c->room("ssj_fres", 2 * (size_t)CF, &fres));
+        AIY_TRY(mark(0));
+        {  // 1. pk [m][3][T][N][Na], path 3i + p with economy i's parameters, grid and shocks
+            EgmBackwardArgs A{};
+            A.N = (int)N; A.Na = (int)Na; A.C = (int)C3; A.T = (int)T;
+            A.group = 3; A.prm = dprm;
+            A.a_stride = (size_t)Na; A.s_stride = (size_t)N; A.P_stride = NN;
+            A.r = dr; A.w = dw; A.pcT = dc; A.pcT_stride = 0; A.pcT_estride = n;
+            A.a = da; A.s = ds; A.P = dP; A.pk = dpk; A.pc = nullptr;
+            A.status = bres; A.fail_t = bres + C3;
+            AIY_TRY(launch_egm_backward_batch(A, c->st));
+        }
+        AIY_TRY(mark(1));
+        {  // 2. Λ1 [m][3][T][N][Na]: one push of economy i's λ through each of its 3T policies
+            DistForwardArgs A{};
+            A.N = (int)N; A.Na = (int)Na; A.C = (int)CF; A.T = 1;
+            A.group = (int)(3 * T); A.a_stride = (size_t)Na; A.P_stride = NN;
+            A.pk = dpk; A.lam0 = dl0; A.lam0_stride = 0; A.lam0_estride = n;
+            A.a = da; A.P = dP; A.K = dK; A.lamT = dl1;
+            A.status = fres; A.fail_t = fres + CF; A.skip = nullptr;
+            AIY_TRY(launch_dist_forward_batch(A, c->st));
+        }
+        AIY_TRY(mark(2));
+        {  // 3. E [m][T][N][Na] of economy i's base period-0 policy, read in place out of pk
+            DistExpectArgs A{};
+            A.N = (int)N; A.Na = (int)Na; A.C = (int)m; A.T = (int)T;
+            A.pk = dpk; A.pk_stride = 3 * (size_t)T * n; A.y0 = dy; A.y0_stride = n;
+            A.a = da; A.a_stride = (size_t)Na; A.P = dP; A.P_stride = NN; A.E = dE;
+            AIY_TRY(launch_dist_expect_batch(A, c->st));
+        }
+        AIY_TRY(mark(3));
+        {  // 4, 5. F and J [m][2][T][T]
+            SsjFakeNewsArgs A{};
+            A.T = (int)T; A.n_in = 2; A.n = (int)n; A.h = h; A.C = (int)m;
+            A.E = dE; A.lam1 = dl1; A.F = dF; A.J = dJ;
+            AIY_TRY(launch_ssj_fake_news(A, c->st));
+        }
+        AIY_TRY(mark(4));
+        std::vector<int> hb(C3), hf(CF);
+        for (int64_t i = 0; i < m; ++i) {
+            const size_t o = (size_t)(e0 + i) * tt;
+            AIY_TRY(c->down(J_r + o, dJ + 2 * i * tt, tt));
+            AIY_TRY(c->down(J_w + o, dJ + (2 * i + 1) * tt, tt));
+            if (F_r) AIY_TRY(c->down(F_r + o, dF + 2 * i * tt, tt));
+            if (F_w) AIY_TRY(c->down(F_w + o, dF + (2 * i + 1) * tt, tt));
+        }
+        if (E) AIY_TRY(c->down(E + (size_t)e0 * T * n, dE, (size_t)m * T * n));
+        AIY_TRY(c->down(hb.data(), bres, (size_t)C3));
+        AIY_TRY(c->down(hf.data(), fres, (size_t)CF));
+        AIY_TRY(c->sync());  // the next chunk reuses the buffers
+        for (int64_t i = 0; i < m; ++i) {
+            int sb = 0, sf = 0;
+            for (int64_t p = 0; p < 3; ++p) sb |= hb[3 * i + p];
+            for (int64_t p = 0; p < 3 * T; ++p) sf |= hf[3 * T * i + p];
+            backward_status[e0 + i] = sb;
+            forward_status[e0 + i] = sf;
+            if (sb | sf) {  // a pass stopped: nothing downstream of it is a derivative
+                double *jr = J_r + (size_t)(e0 + i) * tt, *jw = J_w + (size_t)(e0 + i) * tt;
+                for (size_t q = 0; q < tt; ++q) jr[q] = jw[q] = nan;
+            }
+        }
+        if (stage_ms)
+            for (int q = 0; q < 4; ++q) {
+                float ms = 0;
+                AIY_HIP(hipEventElapsedTime(&ms, ev[q], ev[q + 1]));
+                stage_ms[q] += ms;
+            }
+    }
     return AIY_OK;
 }
 

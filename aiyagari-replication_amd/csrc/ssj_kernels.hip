@@ -22,6 +22,11 @@
 // the other inputs or the launch: no atomics, no split of k across workgroups.
 //
 // ssj_jacobian_kernel — one thread per diagonal of one input: J = F + J(t−1, s−1), t ascending.
+//
+// Several economies in one launch (aiy_ssj_jacobian_batch): the expectation pass reads economy
+// c's policy, grid and P through strides; the contraction and the diagonals take the economy in
+// the grid, z = c·n_in + x, with E, Λ1, F and J blocks at c · (the block's size).  Nothing an
+// entry is computed from depends on C.
 #include "aiy_common.hpp"
 #include "ssj.hpp"
 
@@ -40,11 +45,13 @@ __global__ __launch_bounds__(1024) void dist_expect_batch_kernel(DistExpectArgs 
     double* const s_P = s_wl + n;
     int* const s_lo = reinterpret_cast<int*>(s_P + 256);
 
-    const double* __restrict__ g = A.pk + (size_t)c * n;
+    const double* __restrict__ g = A.pk + (size_t)c * (A.pk_stride ? A.pk_stride : (size_t)n);
     const double* __restrict__ y = A.y0 + (size_t)c * A.y0_stride;
     double* __restrict__ Ec = A.E + (size_t)c * T * n;
-    for (int q = tid; q < N * N; q += nthr) s_P[q] = A.P[q];
-    for (int k = tid; k < Na; k += nthr) s_G[k] = A.a[k];  // (Na <= n: a_grid in G's array)
+    const double* __restrict__ P_e = A.P + (size_t)c * A.P_stride;
+    const double* __restrict__ a_e = A.a + (size_t)c * A.a_stride;
+    for (int q = tid; q < N * N; q += nthr) s_P[q] = P_e[q];
+    for (int k = tid; k < Na; k += nthr) s_G[k] = a_e[k];  // (Na <= n: a_grid in G's array)
     for (int e = tid; e < n; e += nthr) {
         const double v = y[e];
         s_E[e] = v;
@@ -117,13 +124,14 @@ __global__ __launch_bounds__(256) void ssj_fake_news_kernel(SsjFakeNewsArgs A) {
     __shared__ double s_e[kFnTile * kFnPitch];
     __shared__ double s_d[kFnTile * kFnPitch];
     const int T = A.T, n = A.n;
-    const int x = blockIdx.z;
+    const int c = blockIdx.z / A.n_in, x = blockIdx.z - c * A.n_in;  // (C = 0 or 1: c = 0)
     const int t0 = blockIdx.y * kFnTile, s0 = blockIdx.x * kFnTile;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lq = lane >> 4;
     const int wt = (wave >> 1) * 16, wsd = (wave & 1) * 16;
-    const double* __restrict__ base = A.lam1;
-    const double* __restrict__ pert = A.lam1 + (size_t)(x + 1) * T * n;
+    const double* __restrict__ Ecn = A.E + (size_t)c * T * n;
+    const double* __restrict__ base = A.lam1 + (size_t)c * (A.n_in + 1) * T * n;
+    const double* __restrict__ pert = base + (size_t)(x + 1) * T * n;
     // this thread's four (row, k) places of a stage: k = tid & 31, rows tid >> 5 + 8·u
     const int lk = tid & (kFnChunk - 1), lrow = tid >> 5;
     ssj_v4d acc = {0.0, 0.0, 0.0, 0.0};
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256) void ssj_fake_news_kernel(SsjFakeNewsArgs A) {
             const int t = t0 + row, s = s0 + row;
             double ev = 0.0, dv = 0.0;
             if (k < n) {
-                if (t < T) ev = A.E[(size_t)t * n + k];
+                if (t < T) ev = Ecn[(size_t)t * n + k];
                 if (s < T) {
                     const size_t o = (size_t)(T - 1 - s) * n + k;
                     dv = (pert[o] - base[o]) / A.h;
@@ -154,7 +162,7 @@ __global__ __launch_bounds__(256) void ssj_fake_news_kernel(SsjFakeNewsArgs A) {
         __syncthreads();
     }
     const int s = s0 + wsd + lr;
-    double* __restrict__ Fx = A.F + (size_t)x * T * T;
+    double* __restrict__ Fx = A.F + (size_t)blockIdx.z * T * T;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int t = t0 + wt + lq + 4 * g;
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(256) void ssj_fake_news_kernel(SsjFakeNewsArgs A) {
     }
 }
 
-// thread q of input x: the diagonal through (max(q − (T−1), 0), max((T−1) − q, 0))
+// thread q of input x (of economy c: blockIdx.y = c·n_in + x): the diagonal through (max(q − (T−1), 0), max((T−1) − q, 0))
 __global__ void ssj_jacobian_kernel(SsjFakeNewsArgs A) {
     const int T = A.T;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -218,10 +226,13 @@ int launch_ssj_fake_news(const SsjFakeNewsArgs& A, hipStream_t st) {
     if (A.T < 1 || A.T > kSsjMaxT || A.n_in < 1 || A.n_in > 65535 || A.n < 1)
         return fail(AIY_BAD_SHAPE, "fake-news contraction needs 1 <= T <= 32768, "
                                    "1 <= n_in <= 65535 and n >= 1");
+    const int64_t nz = (int64_t)(A.C > 0 ? A.C : 1) * A.n_in;
+    if (A.C < 0 || nz > 65535)
+        return fail(AIY_BAD_SHAPE, "fake-news contraction needs C·n_in <= 65535");
     const int nt = (A.T + kFnTile - 1) / kFnTile;
-    ssj_fake_news_kernel<<<dim3(nt, nt, A.n_in), 256, 0, st>>>(A);
+    ssj_fake_news_kernel<<<dim3(nt, nt, (unsigned)nz), 256, 0, st>>>(A);
     AIY_HIP(hipGetLastError());
-    ssj_jacobian_kernel<<<dim3((2 * A.T - 1 + 255) / 256, A.n_in), 256, 0, st>>>(A);
+    ssj_jacobian_kernel<<<dim3((2 * A.T - 1 + 255) / 256, (unsigned)nz), 256, 0, st>>>(A);
     AIY_HIP(hipGetLastError());
     return AIY_OK;
 }

@@ -33,6 +33,14 @@ struct EgmBackwardArgs {
     // the labour pass only (launch_labor_egm_backward_batch)
     double phi, theta;
     double* pl;  // device [C][T][N][Na]
+    // Paths of several economies in one launch (launch_egm_backward_batch only; all zero: one
+    // economy, as above).  group > 0: path c belongs to economy e = c / group and reads
+    // a + e·a_stride, s + e·s_stride, P + e·P_stride and pcT + c·pcT_stride + e·pcT_estride;
+    // prm (nullable) is device [C/group][3], economy e's (β, σ, amin), which then replace beta,
+    // sigma and amin, with ns = is_int_ge(σ, 1) ? (int)σ : 0 formed per economy.
+    int group;
+    size_t a_stride, s_stride, P_stride, pcT_estride;
+    const double* prm;
 };
 inline bool egm_backward_fits(int64_t N, int64_t Na) { return egm_batch_fits(N, Na, false); }
 int launch_egm_backward_batch(const EgmBackwardArgs& A, hipStream_t st);
@@ -66,6 +74,11 @@ struct DistForwardArgs {
     const double* pl;    // device [C][T][N][Na]
     const double* s;     // device [N]
     double* H;           // device [C][T]
+    // Paths of several economies in one launch (all zero: one economy, as above).  group > 0:
+    // path c belongs to economy e = c / group and reads a + e·a_stride, P + e·P_stride and
+    // lam0 + c·lam0_stride + e·lam0_estride.  (The pass with hours reads one s for all.)
+    int group;
+    size_t a_stride, P_stride, lam0_estride;
 };
 // LDS of one workgroup: dist_solve_batch_kernel<true>'s (λ, mass, lottery weights, run offsets,
 // scratch) and a_grid.  The period's keys and the partial sums of K live in the mass array, which

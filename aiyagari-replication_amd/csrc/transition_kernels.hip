@@ -33,6 +33,11 @@
 // forward pass plus H[t] = Σ λ_t·(s_j·pl_t): its block sums are formed beside K[t]'s in step A
 // (pl_t read from global memory, s [16] in LDS after a_grid) and folded beside K[t] in step B,
 // before the period's monotonicity decision.  <false> reads and writes nothing of it.
+//
+// Paths of several economies in one launch (aiy_ssj_jacobian_batch): with group > 0, path c
+// belongs to economy c / group and reads that economy's grid, shocks, P and start array through
+// strides, the backward pass also its (β, σ, amin) from a device array.  All-zero fields are the
+// one-economy launch, operation for operation; the labour kernels do not read them.
 #include "aiy_common.hpp"
 #include "dist_dev.hpp"
 #include "egm_dev.hpp"
@@ -57,11 +62,18 @@ __global__ __launch_bounds__(1024) void egm_backward_batch_kernel(EgmBackwardArg
     const int nthr = blockDim.x;  // 1,024 >= N·N
     const double* __restrict__ rc = A.r + (size_t)cand * (T + 1);
     const double* __restrict__ wc = A.w + (size_t)cand * T;
-    const double* __restrict__ c0 = A.pcT + (size_t)cand * A.pcT_stride;
-    const double p_reg = tid < N * N ? A.P[tid] : 0.0;
-    const double s_reg = tid < N ? A.s[tid] : 0.0;
+    // this path's economy (group = 0: the one economy of the launch) and its parameters
+    const size_t econ = A.group > 0 ? (size_t)(cand / A.group) : 0;
+    const double* __restrict__ c0 = A.pcT + (size_t)cand * A.pcT_stride + econ * A.pcT_estride;
+    const double* __restrict__ a_e = A.a + econ * A.a_stride;
+    const double beta = A.prm ? A.prm[3 * econ] : A.beta;
+    const double sigma = A.prm ? A.prm[3 * econ + 1] : A.sigma;
+    const double amin = A.prm ? A.prm[3 * econ + 2] : A.amin;
+    const int ns = A.prm ? (is_int_ge(sigma, 1.0) ? (int)sigma : 0) : A.ns;
+    const double p_reg = tid < N * N ? A.P[econ * A.P_stride + tid] : 0.0;
+    const double s_reg = tid < N ? A.s[econ * A.s_stride + tid] : 0.0;
     for (int e = tid; e < n; e += nthr) s_c[e] = c0[e];
-    for (int k = tid; k < Na; k += nthr) s_y[k] = A.a[k];
+    for (int k = tid; k < Na; k += nthr) s_y[k] = a_e[k];
 
     // element e = j·Na + a of this thread's strided walk, without a division per element
     const int j0 = tid / Na, a0 = tid - j0 * Na;
@@ -72,7 +84,7 @@ __global__ __launch_bounds__(1024) void egm_backward_batch_kernel(EgmBackwardArg
     for (int t = T - 1; t >= 0; --t) {
         // the next period's prices, in flight during this one
         const double r_pre = t > 0 ? rc[t - 1] : 0.0, w_pre = t > 0 ? wc[t - 1] : 0.0;
-        const double coef0 = A.beta * (1 + r_next);
+        const double coef0 = beta * (1 + r_next);
         if (tid < N * N) s_P[tid] = coef0 * p_reg;
         if (tid < N) s_ws[tid] = w_now * s_reg;
         __syncthreads();
@@ -81,8 +93,8 @@ __global__ __launch_bounds__(1024) void egm_backward_batch_kernel(EgmBackwardArg
             for (int e = tid; e < n; e += nthr) {
                 double acc = 0.0;
                 for (int q = 0; q < N; ++q)
-                    acc = acc + s_P[j * N + q] * uprime_dev(s_c[q * Na + a_i], A.sigma, A.ns);
-                const double cn = aiy_pow(acc, -1.0 / A.sigma);
+                    acc = acc + s_P[j * N + q] * uprime_dev(s_c[q * Na + a_i], sigma, ns);
+                const double cn = aiy_pow(acc, -1.0 / sigma);
                 s_x[e] = ((cn + s_y[a_i]) - s_ws[j]) / (1 + r_now);
                 a_i += da;
                 j += dj;
@@ -103,7 +115,7 @@ __global__ __launch_bounds__(1024) void egm_backward_batch_kernel(EgmBackwardArg
                 const double q = s_y[a_i];
                 double g = egm_batch_interp(x, s_y, Na, q);
                 if (a_i > 0 && !(x[a_i - 1] < x[a_i])) bad = true;
-                if (g < A.amin) g = A.amin;
+                if (g < amin) g = amin;
                 const double cn = ((1 + r_now) * q + s_ws[j]) - g;
                 s_c[e] = cn;  // this thread's own element: the next step's pc_{t+1}
                 pk_t[e] = g;
@@ -329,11 +341,15 @@ __global__ __launch_bounds__(1024) void dist_forward_batch_kernel(DistForwardArg
     double* const s_hpart = n >= 4 ? s_part + ((n + 255) >> 8) : s_P + 256;
     const double* __restrict__ plc = HOURS ? A.pl + (size_t)cand * T * n : nullptr;
 
-    const double* __restrict__ l0 = A.lam0 + (size_t)cand * A.lam0_stride;
+    // this path's economy (group = 0: the one economy of the launch)
+    const size_t econ = A.group > 0 ? (size_t)(cand / A.group) : 0;
+    const double* __restrict__ l0 = A.lam0 + (size_t)cand * A.lam0_stride + econ * A.lam0_estride;
     const double* __restrict__ pkc = A.pk + (size_t)cand * T * n;
-    for (int q = tid; q < N * N; q += nthr) s_P[q] = A.P[q];
+    const double* __restrict__ P_e = A.P + econ * A.P_stride;
+    const double* __restrict__ a_e = A.a + econ * A.a_stride;
+    for (int q = tid; q < N * N; q += nthr) s_P[q] = P_e[q];
     for (int e = tid; e < n; e += nthr) s_lam[e] = l0[e];
-    for (int k = tid; k < Na; k += nthr) s_a[k] = A.a[k];
+    for (int k = tid; k < Na; k += nthr) s_a[k] = a_e[k];
     if (HOURS && tid < N) s_s[tid] = A.s[tid];
     double xk[kFwdPerThread];  // this thread's states of the coming period's pk
 #pragma unroll

@@ -17,7 +17,7 @@ import numpy as np
 
 from ._capi import check, i64, ip, lib, ptr
 from .transition import (_f, _labor_newton_matrix, _labor_response, _newton_matrix,
-                         _price_slopes, _ratio_slopes)
+                         _price_slopes, _ratio_slopes, jacobian_batch)
 
 OUTPUTS = ("K", "Y", "C", "r", "w")
 OUTPUTS_LABOR = ("K", "Y", "C", "r", "w", "H")
@@ -187,6 +187,113 @@ def autocovariance_batch(m, L):
     check(lib().aiy_ssj_loglik_batch(i64(n_c), i64(n_o), i64(T), i64(L), ptr(m), None, None, ip(1),
                                      None, None, None, ptr(Gam), None))
     return Gam
+
+
+def dense_solve_batch(A, B, chunk=0):
+    """aiy_dense_solve_batch: A [C][n][n], B [C][n][R] (or [C][n]: R = 1) -> dict(X (B's shape),
+    status [C], fail [C]).  Gaussian elimination with partial pivoting, one workgroup per system,
+    in the header's operation order; status 1: column `fail` had no finite non-zero pivot (X NaN)
+    — that system only.  chunk: systems staged at a time (0: the 4 GiB default)."""
+    A, B = _f(A), _f(B)
+    if A.ndim == 2:
+        A, B = A[None], B[None]
+    vec = B.ndim == 2
+    B3 = B[:, :, None] if vec else B
+    if A.ndim != 3 or A.shape[1] != A.shape[2] or B3.ndim != 3 or B3.shape[:2] != A.shape[:2]:
+        raise ValueError("A must be [C][n][n] and B [C][n][R] or [C][n]")
+    B3 = np.ascontiguousarray(B3)
+    n_c, n, R = B3.shape
+    X = np.empty((n_c, n, R))
+    st, fl = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_dense_solve_batch(i64(n_c), i64(n), i64(R), ptr(A), ptr(B3), ptr(X), ptr(st),
+                                      ptr(fl), i64(chunk)))
+    return dict(X=X[:, :, 0] if vec else X, status=st, fail=fl)
+
+
+def dense_solve_batch_dev(A, B, X, work, status, fail, stream=None):
+    """aiy_dense_solve_batch_dev (torch tensors): A [C][n][n], B [C][n][R], X [C][n][R] (out), work
+    [C][n][n+R] (float64 scratch), status, fail (int32) [C].  Enqueues only."""
+    from ._capi import stream_handle
+    check(lib().aiy_dense_solve_batch_dev(i64(A.shape[0]), i64(A.shape[1]), i64(B.shape[2]),
+                                          ptr(A), ptr(B), ptr(X), ptr(work), ptr(status),
+                                          ptr(fail), stream_handle(stream)))
+
+
+def _ge_system(ss, J_r, J_w, dZ):
+    """Economy's GE system for one shock path dZ [T]: (I − M, b) with M of _newton_matrix and
+    b = J_r·(r_Z·dZ) + J_w·(w_Z·dZ)."""
+    _, _, r_Z, w_Z = _price_slopes(ss)
+    A = -_newton_matrix(ss, dict(J_r=J_r, J_w=J_w))
+    return A, J_r @ (r_Z * dZ) + J_w @ (w_Z * dZ)
+
+
+def _ge_outputs(ss, x, dZ, outputs):
+    """ge_jacobians' formulas on the vector x (row t is K_{t+1}) rather than on the matrix X."""
+    r_K, w_K, r_Z, w_Z = _price_slopes(ss)
+    alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]
+    G = {"K": np.zeros_like(x)}
+    G["K"][1:] = x[:-1]
+    G["r"] = r_K * G["K"] + r_Z * dZ
+    G["w"] = w_K * G["K"] + w_Z * dZ
+    Y_ss = (ss["r"] + delta) * ss["K"] / alpha
+    G["Y"] = Y_ss * dZ + (ss["r"] + delta) * G["K"]
+    G["C"] = G["Y"] - x + (1 - delta) * G["K"]
+    return _pick(G, outputs)
+
+
+def ge_ma_batch(ss_list, jac_batch, dZ, outputs=OUTPUTS, solve=None, chunk=0):
+    """m [C][n_o][T], the observables' MA coefficients of C economies, economy c under its own
+    shock path dZ[c] [T]: m[c] = ge_jacobians(ss_c, jac_c, outputs) @ dZ[c] without forming G —
+    one right-hand side per economy instead of T.  The host forms b_c = J_r[c]·(r_Z·dZ_c) +
+    J_w[c]·(w_Z·dZ_c) and I − M_c (_newton_matrix); ONE dense_solve_batch call with R = 1 gives
+    x_c, whose row t is K_{t+1}; K, r, w, Y and C follow by ge_jacobians' formulas.  jac_batch:
+    jacobian_batch's dict (J_r, J_w [C][T][T]).  An economy whose solve stops (status 1) has NaN
+    rows.  solve: dense_solve_batch's signature (the tests' CPU reference)."""
+    ss_list = list(ss_list)
+    J_r, J_w, dZ = _f(jac_batch["J_r"]), _f(jac_batch["J_w"]), np.atleast_2d(_f(dZ))
+    n_c = len(ss_list)
+    if J_r.ndim != 3 or J_r.shape != J_w.shape or J_r.shape[0] != n_c or \
+            dZ.shape != (n_c, J_r.shape[1]):
+        raise ValueError("jac_batch must hold J_r, J_w [C][T][T] and dZ must be [C][T]")
+    sys_ = [_ge_system(ss_list[c], J_r[c], J_w[c], dZ[c]) for c in range(n_c)]
+    A, b = np.stack([q[0] for q in sys_]), np.stack([q[1] for q in sys_])
+    out = (solve or dense_solve_batch)(A, b, chunk=chunk)
+    m = np.stack([_ge_outputs(ss_list[c], out["X"][c], dZ[c], outputs) for c in range(n_c)])
+    m[out["status"] != 0] = np.nan  # (K_0 = 0 and the impact terms would survive a NaN x)
+    return m
+
+
+def structural_loglik(ss_list, y, rho, sigma_e, me_var, T, outputs=("Y", "C", "K"), h=1e-4,
+                      split_ms=None):
+    """The log-likelihoods of C structural candidates, candidate c = (the economy ss_list[c], the
+    AR(1) shock (rho[c], sigma_e[c])), against one observed panel y [L][n_o]: jacobian_batch,
+    ar1_ma, ge_ma_batch and loglik_batch chained — four launches' worth of device work for the
+    whole batch.  Returns dict(loglik, status, fail [C], jac_status [C][2]); a candidate's bits do
+    not depend on the batch.  split_ms: an optional float64 [4] array that receives the host
+    clock's split in ms: Jacobians, host assembly, solve, likelihood."""
+    import time
+    ss_list = list(ss_list)
+    t0 = time.perf_counter()
+    jac = jacobian_batch(ss_list, T, h, want_F=False, want_E=False)
+    t1 = time.perf_counter()
+    dZ = ar1_ma(rho, sigma_e, T)
+    took = {}
+
+    def timed_solve(A, b, chunk=0):
+        ts = time.perf_counter()
+        out = dense_solve_batch(A, b, chunk=chunk)
+        took["solve"] = time.perf_counter() - ts
+        return out
+
+    m = ge_ma_batch(ss_list, jac, dZ, outputs, solve=timed_solve)
+    t2 = time.perf_counter()
+    out = loglik_batch(m, y, me_var)
+    t3 = time.perf_counter()
+    if split_ms is not None:
+        split_ms[:] = [1e3 * (t1 - t0), 1e3 * (t2 - t1 - took["solve"]), 1e3 * took["solve"],
+                       1e3 * (t3 - t2)]
+    out["jac_status"] = jac["status"]
+    return out
 
 
 def moments(Gamma, lags=(0, 1)):

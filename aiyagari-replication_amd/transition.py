@@ -294,6 +294,49 @@ def jacobian(ss, T, h=1e-4, stage_ms=None):
     return dict(J_r=J_r, J_w=J_w, F_r=F_r, F_w=F_w, E=E, status=(sb.value, sf.value))
 
 
+def jacobian_batch(ss_list, T, h=1e-4, stage_ms=None, chunk=0, want_F=True, want_E=True):
+    """aiy_ssj_jacobian_batch: jacobian() of C steady states (a list of steady_state's dicts with
+    one N and one Na; everything else — β, σ, amin, the grid, the shocks, r, w — is the
+    economy's own) in one call, each stage one launch over a chunk of economies.  Returns
+    dict(J_r, J_w, F_r, F_w [C][T][T], E [C][T][N][Na], status [C][2] (backward, forward));
+    economy e's arrays are jacobian(ss_list[e], T, h)'s bit for bit, whatever the batch.
+    stage_ms: an optional float64 [4] array that receives the four stages' device times;
+    chunk: economies staged at a time (0: as many as fit the 4 GiB cap); want_F, want_E: False
+    leaves F_r, F_w or E out of the dict and on the device (E is T·N·Na doubles an economy)."""
+    ss_list = list(ss_list)
+    if not ss_list:
+        raise ValueError("jacobian_batch needs at least one steady state")
+    N, Na = _f(ss_list[0]["cal"]["s"]).size, _f(ss_list[0]["cal"]["a_grid"]).size
+    for e, ss in enumerate(ss_list):
+        cal = ss["cal"]
+        if _f(cal["s"]).size != N or _f(cal["a_grid"]).size != Na:
+            raise ValueError(f"economy {e} has another N or Na than economy 0")
+        if _f(ss["policy_c"]).shape != (N, Na) or _f(ss["lam"]).shape != (N, Na):
+            raise ValueError(f"economy {e}: ss['policy_c'] and ss['lam'] must be [N][Na]")
+    n_c = len(ss_list)
+    col = lambda f: np.ascontiguousarray(np.stack([_f(f(ss)) for ss in ss_list]))
+    pc, lam = col(lambda ss: ss["policy_c"]), col(lambda ss: ss["lam"])
+    a, s = col(lambda ss: ss["cal"]["a_grid"]), col(lambda ss: ss["cal"]["s"])
+    P = col(lambda ss: _f(ss["cal"]["P"]).T)  # each block column-major
+    r, w = col(lambda ss: ss["r"]), col(lambda ss: ss["w"])
+    beta, sigma, amin = (col(lambda ss, k=k: ss["cal"][k]) for k in ("beta", "sigma", "amin"))
+    Tn = max(int(T), 0)
+    J_r, J_w = np.empty((n_c, Tn, Tn)), np.empty((n_c, Tn, Tn))
+    F_r, F_w = (np.empty((n_c, Tn, Tn)), np.empty((n_c, Tn, Tn))) if want_F else (None, None)
+    E = np.empty((n_c, Tn, N, Na)) if want_E else None
+    sb, sf = np.zeros(n_c, np.int32), np.zeros(n_c, np.int32)
+    check(lib().aiy_ssj_jacobian_batch(i64(n_c), ptr(pc), ptr(lam), ptr(r), ptr(w), ptr(a), ptr(s),
+                                       ptr(P), i64(N), i64(Na), ptr(beta), ptr(sigma), ptr(amin),
+                                       i64(T), d(h), ptr(J_r), ptr(J_w), ptr(F_r), ptr(F_w),
+                                       ptr(E), ptr(sb), ptr(sf), ptr(stage_ms), i64(chunk)))
+    out = dict(J_r=J_r, J_w=J_w, status=np.stack([sb, sf], axis=1))
+    if want_F:
+        out.update(F_r=F_r, F_w=F_w)
+    if want_E:
+        out["E"] = E
+    return out
+
+
 def _price_slopes(ss):
     """∂r/∂K, ∂w/∂K, ∂r/∂Z, ∂w/∂Z of prices_from_K at the steady state."""
     alpha, delta = ss["cal"]["alpha"], ss["cal"]["delta"]

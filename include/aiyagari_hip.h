@@ -715,6 +715,31 @@ int aiy_ssj_jacobian(const double* policy_c, const double* lambda, double r_ss, 
                      int64_t Na, double beta, double sigma, double amin, int64_t T, double h,
                      double* J_r, double* J_w, double* F_r, double* F_w, double* E,
                      int32_t* backward_status, int32_t* forward_status, double* stage_ms);
+/* aiy_ssj_jacobian of C steady states in one call: the same four stages, each ONE launch over the
+ * economies of a chunk (3 backward paths, 3T one-step pushes, 1 expectation pass and 2 T x T
+ * tiles' worth of workgroups per economy).  Economy e has its own policy_c[e], lambda[e]
+ * ([N][Na]), r_ss[e], w_ss[e], beta[e], sigma[e], amin[e], a_grid[e] [Na], s[e] [N] and P[e]
+ * (N x N column-major); N, Na, T and h are shared.  J_r, J_w: [C][T][T]; F_r, F_w [C][T][T] and
+ * E [C][T][N][Na] are nullable; backward_status, forward_status: [C]; stage_ms (nullable): [4],
+ * summed over the chunks.
+ * Economy e's outputs equal aiy_ssj_jacobian's on e alone bit for bit and do not depend on C, on
+ * e's place in the batch or on the chunking.  An economy with a pass that stopped gets its status
+ * words (the OR over its paths) and NaN J_r, J_w; the others are not touched by it.
+ * Memory: the period policies and Lambda1 are 3 T N Na doubles each per economy, so the entry
+ * works through the economies `chunk` at a time; chunk = 0: as many as fit 4 GiB of device
+ * memory (8 (7 T N Na + 4 T^2) bytes an economy), at least one.
+ * Refused before any device is asked for, in this order: NULL arguments (the nullable ones
+ * apart); C outside [1, 2^24]; N, Na, the fit rules, T and h as aiy_ssj_jacobian; chunk outside
+ * [0, 32767]; then per economy e = 0 .. C-1, the message starting "economy e: ": a grid that is
+ * not finite and strictly increasing, r_ss not finite or 1 + r_ss <= 0, w_ss not finite, beta
+ * or sigma not finite or <= 0, amin not finite. */
+int aiy_ssj_jacobian_batch(int64_t C, const double* policy_c, const double* lambda,
+                           const double* r_ss, const double* w_ss, const double* a_grid,
+                           const double* s, const double* P, int64_t N, int64_t Na,
+                           const double* beta, const double* sigma, const double* amin, int64_t T,
+                           double h, double* J_r, double* J_w, double* F_r, double* F_w, double* E,
+                           int32_t* backward_status, int32_t* forward_status, double* stage_ms,
+                           int64_t chunk);
 
 /* ---- Transition paths of the endogenous-labour economy (A5; new).  The same five entries and the
  * same conventions as above.  Fit rules (else AIY_BAD_ARG, no per-step fallback):
@@ -829,6 +854,28 @@ int aiy_ssj_loglik_batch_dev(int64_t C, int64_t n_o, int64_t T, int64_t L, const
 int aiy_ssj_loglik_batch(int64_t C, int64_t n_o, int64_t T, int64_t L, const double* m,
                          const double* y, const double* me_var, int me_var_shared, double* loglik,
                          int32_t* status, int32_t* fail, double* Gamma, double* d);
+
+/* ---- Dense solve, many systems per launch (new).  C systems A_c X_c = B_c by Gaussian
+ * elimination with partial pivoting, ONE workgroup per system.  All arrays row-major: A [C][n][n],
+ * B [C][n][R], X [C][n][R] (out), status and fail [C].  A and B are not modified: the kernel
+ * works on a copy (A_c | B_c) in `work`, device [C][n][n+R].  No fused multiply-adds:
+ *   1. j = 0 .. n-1: p = j, best = |A[j][j]|; i = j+1 .. n-1 ascending: |A[i][j]| > best takes it
+ *      (ties: the lowest index; a NaN is never taken over a number).  Unless best > 0 and finite:
+ *      status 1, fail j, the whole X block NaN, stop.  Swap rows j and p of A and of B.  i > j:
+ *      l_i = A[i][j] / A[j][j], A[i][k] = A[i][k] - (l_i A[j][k]) for k > j, B[i][q] = B[i][q] -
+ *      (l_i B[j][q]);
+ *   2. j = n-1 .. 0: X[j][q] = B[j][q] / A[j][j]; B[i][q] = B[i][q] - (A[i][j] X[j][q]), i < j;
+ *   3. status 0, fail -1.
+ * A system's bits do not depend on C, on its place in the batch, on the other systems or on the
+ * run.  Refused before any device is asked for: NULL arguments, C < 1, n outside [1, 4096],
+ * R < 1, n (n + R) >= 2^31, chunk < 0.  The device entry only enqueues on `stream`.  The host
+ * entry stages `chunk` systems at a time; chunk = 0: as many as fit 4 GiB of device memory
+ * (16 (n^2 + n R) bytes a system), at least one. */
+int aiy_dense_solve_batch_dev(int64_t C, int64_t n, int64_t R, const double* A, const double* B,
+                              double* X, double* work, int32_t* status, int32_t* fail,
+                              void* stream);
+int aiy_dense_solve_batch(int64_t C, int64_t n, int64_t R, const double* A, const double* B,
+                          double* X, int32_t* status, int32_t* fail, int64_t chunk);
 
 /* ---- A6/A7 device tier for one process per GPU.  A handle owns the shard
  * K in [K0, K1) of all four s; V / Vold / Vout / kopt are full k x K x S column-major device
